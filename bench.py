@@ -9,7 +9,7 @@ executor whose probabilities are fp32-grade (2 - 4e-6 off fp32 on the trained fi
 the same detected point set: tests/test_gpu_trained_parity.py), i.e. the one that meets the north
 star's gate.  Plain f16 / bf16 (3x the rate, ~1e-3 / ~8e-3 off) and fp32 are legs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of FplNetwork.infer's hot path (normalise -> tile lattice ->
@@ -18,9 +18,17 @@ both resident in HBM.  With N ranks the volume is N x `size` rows along Z and ev
 rank takes a contiguous slab of tile rows (weak scaling, no collective on the
 data path; RCCL is only used for the barrier / max-over-ranks of the clock).
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel from HIP
-events recorded on the library's stream during the timed steps; `cpu_baseline`
-times the CPU oracle (torch-CPU restatement, NOT Keras) on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and
+prints the headline (`value`, `ms_per_step`); `roofline` and the `*_1024` / host-to-host
+figures are null, `cpu_baseline` and `legs` absent.  `--full` adds them: `roofline` prices the
+dominant kernel from HIP events recorded on the library's stream during the timed steps,
+`cpu_baseline` times the CPU oracle (torch-CPU restatement, NOT Keras) on a bounded sample,
+`legs` are the secondary workloads (secondary_legs).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed - the
+float32 probability volume a caller of the step receives - as a fixed sample (dump_outputs),
+so that two builds can be compared output for output: inputs and weights are seeded and
+the same from run to run for the same arguments.
 """
 import argparse
 import json
@@ -337,6 +345,39 @@ def secondary_legs(ctx, torch, prog, tile, off, size, steps):
     return legs
 
 
+DUMP_SAMPLES = 1 << 22                # voxels of the seeded random sample (16 MiB as float32)
+DUMP_PLANE_BYTES = 32 << 20           # budget of the whole z planes beside it
+DUMP_SEED = 20251016
+
+
+def dump_outputs(out_dir, dst, off, suffix=''):
+    """The float32 probability volume the timed step left in `dst` (this rank's slab), as
+    .npy files in `out_dir` (at most 48 MiB in all; only the valid region - `off` voxels in
+    from every face - which the step writes in full):
+      prob_sample<suffix>.npy  float32 (n,): the voxels at a fixed seeded random set of
+                               positions of the valid region, in raster order
+      prob_planes<suffix>.npy  float32 (k, Y', X'): up to three whole valid z planes, at 1/4,
+                               1/2 and 3/4 of the valid depth (as many as fit the budget)
+    Positions depend only on the volume's shape, so equal arguments give comparable files."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    D, H, W = dst.shape
+    vd, vh, vw = D - 2 * off, H - 2 * off, W - 2 * off
+    n_valid = vd * vh * vw
+    rng = np.random.default_rng(DUMP_SEED)
+    flat = np.unique(rng.integers(0, n_valid, min(DUMP_SAMPLES, n_valid), dtype=np.int64))
+    z, rem = np.divmod(flat, vh * vw)
+    y, x = np.divmod(rem, vw)
+    idx = ((z + off) * H + (y + off)) * W + (x + off)
+    sample = dst.reshape(-1)[torch.from_numpy(idx).to(dst.device)].cpu().numpy()
+    np.save(os.path.join(out_dir, 'prob_sample%s.npy' % suffix), sample.astype(np.float32))
+    k = int(min(3, DUMP_PLANE_BYTES // (vh * vw * 4)))
+    zs = [off + (vd - 1) * (i + 1) // 4 for i in range(k)]
+    planes = np.stack([dst[z, off:H - off, off:W - off].cpu().numpy() for z in zs]) if zs \
+        else np.zeros((0, vh, vw), np.float32)
+    np.save(os.path.join(out_dir, 'prob_planes%s.npy' % suffix), planes.astype(np.float32))
+
+
 def spawn_ranks(n, timeout=None):
     """`python bench.py --gpus N` without a launcher: N children of this script, one per GPU
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torchrun would), started before this
@@ -467,14 +508,23 @@ def main():
                          'reference arithmetic on fp32 MFMAs')
     ap.add_argument('--tile', type=int, default=102,
                     help='reference infer_sz (tile lattice pitch = tile-14)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='beyond the headline: per-kernel HIP-event times of the timed steps and '
+                         'the dominant kernel\'s roofline, the CPU baseline and the secondary legs')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write a fixed sample of what the last step '
+                         'computed as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='print the cpu_baseline object and exit (what the main run spawns)')
     ap.add_argument('--no-legs', action='store_true',
-                    help='skip the secondary legs (other precisions / sizes / configs)')
+                    help='with --full: skip the secondary legs (other precisions / sizes / configs)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process-group backend (gloo only to rehearse N>1 on one GPU)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process only launches - one fresh child per
@@ -494,7 +544,7 @@ def main():
     # 16-thread pool and buffers are gone when the GPU legs run back to back to the end of
     # this process (left in-process, the pool cost the host-bound legs ~0.4 ms per call)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         import subprocess
         r = subprocess.run([sys.executable, os.path.abspath(__file__), '--cpu-baseline-only'],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -559,15 +609,18 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    ctx.timing(True)
-    ctx.timing_reset()
+    if args.full:                       # per-kernel HIP events around every launch
+        ctx.timing(True)
+        ctx.timing_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     dt = time.perf_counter() - t0
-    timings = ctx.timing_get()
-    ctx.timing(False)
+    timings = {}
+    if args.full:
+        timings = ctx.timing_get()
+        ctx.timing(False)
     executor = ctx.last_path()
     n_seen = 1
     if world > 1:
@@ -576,6 +629,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         n_seen = ranks_seen(dist, args.backend)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dst, off, '_rank%d' % rank if world > 1 else '')
     del src, dst
 
     # HBM bytes per launch of each kernel: NOT measured in this run - read from the
@@ -585,7 +640,7 @@ def main():
     traffic_by_kernel = {}
     import glob
     cands = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_hbm_%d_%s.json'
-                                          % (args.size, args.precision))))
+                                          % (args.size, args.precision)))) if args.full else []
     pmc_path = cands[-1] if cands else ''       # the latest round's pass
     if world == 1 and pmc_path:
         for k, v in json.load(open(pmc_path))['kernels'].items():
@@ -627,7 +682,7 @@ def main():
                 roof['mfma_products_per_multiply'] = 3
 
     legs = None
-    if world == 1 and not args.no_legs:
+    if world == 1 and args.full and not args.no_legs:
         legs = secondary_legs(ctx, torch, prog, tile, off, args.size, args.steps)
 
     if rank == 0:

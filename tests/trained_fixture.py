@@ -1,6 +1,8 @@
 """The trained-weights parity fixture: synthetic blob regions, the training recipes that
 produced tests/golden/trained_*.npz (tools/make_trained_fixture.py, run once on a GPU
-box) and a loader that puts those weights into an `FplNetwork`."""
+box) and a loader that puts those weights into an `FplNetwork`.  A file over 1 MiB is
+committed in parts (split_npz)."""
+import io
 import os
 
 import numpy as np
@@ -43,8 +45,34 @@ def blob_region_u8(seed, n, **kw):
     return u8, labels, locs
 
 
+PART_BYTES = 1000000         # a committed file stays under 1 MiB
+
+
+def split_npz(path):
+    """replace `path` by <path>.part0, .part1, ... of at most PART_BYTES each when it is
+    larger (the bytes of the .npz, cut in order); trained_weights joins them again"""
+    data = open(path, 'rb').read()
+    if len(data) <= PART_BYTES:
+        return [path]
+    parts = []
+    for i in range(0, len(data), PART_BYTES):
+        parts.append('%s.part%d' % (path, i // PART_BYTES))
+        with open(parts[-1], 'wb') as f:
+            f.write(data[i:i + PART_BYTES])
+    os.remove(path)
+    return parts
+
+
 def trained_weights(name):
-    with np.load(os.path.join(GOLDEN, 'trained_%s.npz' % name)) as z:
+    path = os.path.join(GOLDEN, 'trained_%s.npz' % name)
+    if not os.path.exists(path):
+        parts, i = [], 0
+        while os.path.exists('%s.part%d' % (path, i)):
+            parts.append(open('%s.part%d' % (path, i), 'rb').read())
+            i += 1
+        assert parts, 'no %s and no parts of it' % path
+        path = io.BytesIO(b''.join(parts))
+    with np.load(path) as z:
         return [z['arr_%d' % i] for i in range(len(z.files))]
 
 

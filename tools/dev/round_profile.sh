@@ -15,7 +15,7 @@ tests)
   python -m pytest tests -m gpu -q > $out/${tag}_tests_gpu.log 2>&1; tail -2 $out/${tag}_tests_gpu.log ;;
 bench)
   # the headline: BASELINE.json's 520^3 volume (bench.py's default), then configs[1]'s 1024^3
-  python bench.py > $out/${tag}_bench520_f16s.json 2> $out/bench_f16s.err
+  python bench.py --full > $out/${tag}_bench520_f16s.json 2> $out/bench_f16s.err
   cut -c1-200 $out/${tag}_bench520_f16s.json
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o bench -- python3 bench.py --no-legs --no-cpu-baseline --steps 20 > $out/trace_bench.json 2> $out/trace.err
   find $out/trace -name '*kernel_stats.csv' -exec cp {} $out/${tag}_bench520_f16s_kernel_stats.csv \;

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from flypylib_amd import FplNetwork, fplmodels, fplobjdetect   # noqa: E402
-from tests.trained_fixture import blob_region, RECIPES         # noqa: E402
+from tests.trained_fixture import blob_region, RECIPES, split_npz   # noqa: E402
 
 
 def train(name):
@@ -49,6 +49,7 @@ def main():
         w = [np.asarray(a, np.float32) for a in net.train_single.get_weights()]
         path = os.path.join(out, 'trained_%s.npz' % name)
         np.savez_compressed(path, *w)
+        split_npz(path)                  # parts of at most 1 MB, as committed
         # what the trained network does on an unseen region, in fp32 and on the 16-bit paths
         r = RECIPES[name]
         net.infer_sz = (r['tile'],) * 3
