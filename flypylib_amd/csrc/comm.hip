@@ -138,7 +138,7 @@ struct CommUse {
 
 extern "C" {
 
-int fpl_comm_unique_id(uint8_t out[FPL_COMM_ID_BYTES]) {
+int fpl_comm_unique_id(uint8_t out[FPL_COMM_ID_BYTES]) try {
   if (!out) return fpl_fail(nullptr, "fpl_comm_unique_id: out is NULL");
   static_assert(sizeof(ncclUniqueId) == FPL_COMM_ID_BYTES, "unique id size");
   FPL_TRY(load_rccl(nullptr));
@@ -146,10 +146,10 @@ int fpl_comm_unique_id(uint8_t out[FPL_COMM_ID_BYTES]) {
   FPL_NCCL(nullptr, g_rccl.GetUniqueId(&id));
   memcpy(out, &id, sizeof(id));
   return 0;
-}
+} FPL_CATCH(nullptr)
 
 int fpl_comm_init(fpl_ctx *ctx, int32_t rank, int32_t nranks,
-                  const uint8_t unique_id[FPL_COMM_ID_BYTES]) {
+                  const uint8_t unique_id[FPL_COMM_ID_BYTES]) try {
   if (!ctx || !unique_id) return fpl_fail(ctx, "fpl_comm_init: NULL argument");
   FPL_REQUIRE(ctx, nranks >= 1 && rank >= 0 && rank < nranks,
               "fpl_comm_init: rank %d of %d", rank, nranks);
@@ -167,9 +167,9 @@ int fpl_comm_init(fpl_ctx *ctx, int32_t rank, int32_t nranks,
   ctx->comm_rank = rank;
   ctx->comm_nranks = nranks;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_comm_destroy(fpl_ctx *ctx) {
+int fpl_comm_destroy(fpl_ctx *ctx) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_comm_destroy: ctx is NULL");
   if (ctx->comm) {
     FPL_HIP(ctx, hipSetDevice(ctx->device));
@@ -177,9 +177,9 @@ int fpl_comm_destroy(fpl_ctx *ctx) {
   }
   fpl_comm_release(ctx);
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_comm_abort(fpl_ctx *ctx) {
+int fpl_comm_abort(fpl_ctx *ctx) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_comm_abort: ctx is NULL");
   // no stream synchronisation: the point is to get out of a collective that will never
   // complete because a peer is gone.  May be called from another host thread: new collectives
@@ -202,18 +202,18 @@ int fpl_comm_abort(fpl_ctx *ctx) {
   }
   ctx->comm_aborting.store(false);
   return 0;
-}
+} FPL_CATCH(ctx)
 
 int fpl_comm_info(fpl_ctx *ctx, int32_t *rank, int32_t *nranks, char *lib_path,
-                  size_t lib_path_cap) {
+                  size_t lib_path_cap) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_comm_info: ctx is NULL");
   if (rank) *rank = ctx->comm ? ctx->comm_rank : 0;
   if (nranks) *nranks = ctx->comm ? ctx->comm_nranks : 0;
   if (lib_path && lib_path_cap) snprintf(lib_path, lib_path_cap, "%s", g_rccl.path);
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_comm_allreduce_sum_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n) {
+int fpl_comm_allreduce_sum_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n) try {
   if (!ctx || !dev_ptr) return fpl_fail(ctx, "fpl_comm_allreduce_sum_f32: NULL argument");
   CommUse use(ctx);
   FPL_REQUIRE(ctx, use.comm != nullptr,
@@ -227,9 +227,9 @@ int fpl_comm_allreduce_sum_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n) {
                                    (ncclComm_t)use.comm, ctx->stream));
   }
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_comm_broadcast_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n, int32_t root) {
+int fpl_comm_broadcast_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n, int32_t root) try {
   if (!ctx || !dev_ptr) return fpl_fail(ctx, "fpl_comm_broadcast_f32: NULL argument");
   CommUse use(ctx);
   FPL_REQUIRE(ctx, use.comm != nullptr,
@@ -240,6 +240,6 @@ int fpl_comm_broadcast_f32(fpl_ctx *ctx, float *dev_ptr, int64_t n, int32_t root
   FPL_NCCL(ctx, g_rccl.Broadcast(dev_ptr, dev_ptr, (size_t)n, ncclFloat, root,
                                  (ncclComm_t)use.comm, ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 }  // extern "C"

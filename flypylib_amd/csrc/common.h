@@ -9,6 +9,7 @@
 #include <cstring>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -133,6 +134,13 @@ int fpl_fail_range_call(fpl_ctx *ctx, const char *fmt, ...);
 #define FPL_RANGE_TAIL 8u
 #define FPL_RANGE_UNET 16u
 int fpl_fail_range(fpl_ctx *ctx, const char *fmt, ...);
+
+// the guard of every C-ABI entry point: no C++ exception crosses the boundary (fplhip.h).
+// Written as a function-try-block, `int fpl_x(...) try { ... } FPL_CATCH(ctx)`; the
+// handler turns the exception in flight into rc 1 and a message naming the function
+int fpl_fail_exception(fpl_ctx *ctx, const char *fn);
+#define FPL_CATCH(ctx_expr)                                                    \
+  catch (...) { return fpl_fail_exception((ctx_expr), __func__); }
 
 #define FPL_HIP(ctx, expr)                                                     \
   do {                                                                         \

@@ -3,37 +3,51 @@
 
 thread_local char g_fpl_err[FPL_MAX_ERR] = {0};
 
-int fpl_fail(fpl_ctx *ctx, const char *fmt, ...) {
+// one formatter behind fpl_fail* : the message goes to the context (if any) and to the
+// thread-local slot that fpl_last_error(NULL) reads; the caller's rc is handed back
+static int fail_v(fpl_ctx *ctx, int rc, const char *fmt, va_list ap) {
   char buf[FPL_MAX_ERR];
-  va_list ap;
-  va_start(ap, fmt);
   vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
   if (ctx) memcpy(ctx->err, buf, sizeof(buf));
   memcpy(g_fpl_err, buf, sizeof(buf));
-  return 1;
+  return rc;
+}
+
+int fpl_fail(fpl_ctx *ctx, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  const int rc = fail_v(ctx, 1, fmt, ap);
+  va_end(ap);
+  return rc;
 }
 
 int fpl_fail_range(fpl_ctx *ctx, const char *fmt, ...) {
-  char buf[FPL_MAX_ERR];
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
+  const int rc = fail_v(ctx, FPL_RC_RANGE, fmt, ap);
   va_end(ap);
-  if (ctx) memcpy(ctx->err, buf, sizeof(buf));
-  memcpy(g_fpl_err, buf, sizeof(buf));
-  return FPL_RC_RANGE;
+  return rc;
 }
 
 int fpl_fail_range_call(fpl_ctx *ctx, const char *fmt, ...) {
-  char buf[FPL_MAX_ERR];
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
+  const int rc = fail_v(ctx, FPL_RC_RANGE_CALL, fmt, ap);
   va_end(ap);
-  if (ctx) memcpy(ctx->err, buf, sizeof(buf));
-  memcpy(g_fpl_err, buf, sizeof(buf));
-  return FPL_RC_RANGE_CALL;
+  return rc;
+}
+
+// called from a catch handler only (FPL_CATCH): rethrows the exception in flight to name it
+int fpl_fail_exception(fpl_ctx *ctx, const char *fn) {
+  try {
+    throw;
+  } catch (const std::bad_alloc &) {
+    return fpl_fail(ctx, "%s: out of host memory", fn);
+  } catch (const std::exception &e) {
+    return fpl_fail(ctx, "%s: %s", fn, e.what());
+  } catch (...) {
+    return fpl_fail(ctx, "%s: unknown C++ exception", fn);
+  }
 }
 
 int fpl_range_flag(fpl_ctx *ctx, unsigned **dev) {
@@ -53,7 +67,7 @@ int fpl_abi_version(void) { return FPL_ABI_VERSION; }
 
 const char *fpl_last_error(fpl_ctx *ctx) { return ctx ? ctx->err : g_fpl_err; }
 
-int fpl_ctx_create(int device_id, fpl_ctx **out) {
+int fpl_ctx_create(int device_id, fpl_ctx **out) try {
   if (!out) return fpl_fail(nullptr, "fpl_ctx_create: out is NULL");
   *out = nullptr;
   int n_dev = 0;
@@ -88,20 +102,17 @@ int fpl_ctx_create(int device_id, fpl_ctx **out) {
       said = true;
     }
   }
-  fpl_ctx *ctx = new fpl_ctx();
+  std::unique_ptr<fpl_ctx, decltype(&fpl_ctx_destroy)> ctx(new fpl_ctx(), fpl_ctx_destroy);
   ctx->device = device_id;
   ctx->n_cu = prop.multiProcessorCount;
-  if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) !=
-      hipSuccess) {
-    delete ctx;
+  if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess)
     return fpl_fail(nullptr, "fpl_ctx_create: hipStreamCreate failed");
-  }
   ctx->stream = ctx->own_stream;
-  *out = ctx;
+  *out = ctx.release();
   return 0;
-}
+} FPL_CATCH(nullptr)
 
-int fpl_ctx_destroy(fpl_ctx *ctx) {
+int fpl_ctx_destroy(fpl_ctx *ctx) try {
   if (!ctx) return 0;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
@@ -122,26 +133,26 @@ int fpl_ctx_destroy(fpl_ctx *ctx) {
   if (ctx->zero_pool) hipFree(ctx->zero_pool);
   if (ctx->range_flag_dev) hipFree(ctx->range_flag_dev);
   if (ctx->range_flag_host) hipHostFree(ctx->range_flag_host);
-  hipStreamDestroy(ctx->own_stream);
+  if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);   // (a context that failed to create)
   delete ctx;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_ctx_set_stream(fpl_ctx *ctx, void *hip_stream) {
+int fpl_ctx_set_stream(fpl_ctx *ctx, void *hip_stream) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_ctx_set_stream: ctx is NULL");
   ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_ctx_synchronize(fpl_ctx *ctx) {
+int fpl_ctx_synchronize(fpl_ctx *ctx) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_ctx_synchronize: ctx is NULL");
   FPL_HIP(ctx, hipSetDevice(ctx->device));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 int fpl_device_info(fpl_ctx *ctx, int32_t *n_cu, int64_t *hbm_bytes, char *name,
-                    size_t name_cap) {
+                    size_t name_cap) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_device_info: ctx is NULL");
   hipDeviceProp_t prop;
   FPL_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -151,31 +162,31 @@ int fpl_device_info(fpl_ctx *ctx, int32_t *n_cu, int64_t *hbm_bytes, char *name,
     snprintf(name, name_cap, "%s (%s)", prop.name, prop.gcnArchName);
   }
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_device_pci_bus_id(fpl_ctx *ctx, char *out, size_t cap) {
+int fpl_device_pci_bus_id(fpl_ctx *ctx, char *out, size_t cap) try {
   if (!ctx || !out || cap < 16) return fpl_fail(ctx, "fpl_device_pci_bus_id: bad argument");
   FPL_HIP(ctx, hipDeviceGetPCIBusId(out, (int)cap, ctx->device));
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_malloc(fpl_ctx *ctx, size_t bytes, void **dev_ptr) {
+int fpl_malloc(fpl_ctx *ctx, size_t bytes, void **dev_ptr) try {
   if (!ctx || !dev_ptr) return fpl_fail(ctx, "fpl_malloc: NULL argument");
   FPL_HIP(ctx, hipSetDevice(ctx->device));
   FPL_HIP(ctx, hipMalloc(dev_ptr, bytes ? bytes : 16));
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_free(fpl_ctx *ctx, void *dev_ptr) {
+int fpl_free(fpl_ctx *ctx, void *dev_ptr) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_free: ctx is NULL");
   FPL_HIP(ctx, hipSetDevice(ctx->device));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   FPL_HIP(ctx, hipFree(dev_ptr));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 int fpl_memcpy(fpl_ctx *ctx, void *dst, int dst_mem, const void *src,
-               int src_mem, size_t bytes) {
+               int src_mem, size_t bytes) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_memcpy: ctx is NULL");
   FPL_HIP(ctx, hipSetDevice(ctx->device));
   hipMemcpyKind kind =
@@ -187,13 +198,13 @@ int fpl_memcpy(fpl_ctx *ctx, void *dst, int dst_mem, const void *src,
   FPL_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_timing_enable(fpl_ctx *ctx, int on) {
+int fpl_timing_enable(fpl_ctx *ctx, int on) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_timing_enable: ctx is NULL");
   ctx->timing = on != 0;
   return 0;
-}
+} FPL_CATCH(ctx)
 
 static int drain_pending(fpl_ctx *ctx) {
   if (ctx->pending.empty()) return 0;
@@ -210,15 +221,15 @@ static int drain_pending(fpl_ctx *ctx) {
   return 0;
 }
 
-int fpl_timing_reset(fpl_ctx *ctx) {
+int fpl_timing_reset(fpl_ctx *ctx) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_timing_reset: ctx is NULL");
   FPL_TRY(drain_pending(ctx));
   for (auto &s : ctx->stats) s = KernelStat();
   return 0;
-}
+} FPL_CATCH(ctx)
 
 int fpl_timing_get(fpl_ctx *ctx, char *names, double *ms, int64_t *launches,
-                   int32_t cap, int32_t *n) {
+                   int32_t cap, int32_t *n) try {
   if (!ctx || !n) return fpl_fail(ctx, "fpl_timing_get: NULL argument");
   FPL_TRY(drain_pending(ctx));
   int32_t m = 0;
@@ -234,7 +245,7 @@ int fpl_timing_get(fpl_ctx *ctx, char *names, double *ms, int64_t *launches,
   }
   *n = m;
   return 0;
-}
+} FPL_CATCH(ctx)
 
 }  // extern "C"
 

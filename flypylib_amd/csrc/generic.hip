@@ -221,7 +221,7 @@ extern "C" {
 int fpl_program_create(fpl_ctx *ctx, const fpl_op *ops, int32_t n_ops,
                        int32_t n_tensors, int32_t out_tensor, const float *arena,
                        int64_t n_arena, const int32_t stride[3],
-                       fpl_program **out) {
+                       fpl_program **out) try {
   if (!ctx || !ops || !out || !arena || !stride)
     return fpl_fail(ctx, "fpl_program_create: NULL argument");
   *out = nullptr;
@@ -250,30 +250,22 @@ int fpl_program_create(fpl_ctx *ctx, const fpl_op *ops, int32_t n_ops,
                   "fpl_program_create: op %d non-positive factor", i);
   }
   FPL_HIP(ctx, hipSetDevice(ctx->device));
-  fpl_program *p = new fpl_program();
+  std::unique_ptr<fpl_program, decltype(&fpl_program_destroy)> p(new fpl_program(), fpl_program_destroy);
   p->ctx = ctx;
   p->ops.assign(ops, ops + n_ops);
   p->n_tensors = n_tensors;
   p->out_tensor = out_tensor;
   for (int a = 0; a < 3; ++a) p->stride[a] = stride[a] > 0 ? stride[a] : 1;
   p->n_arena = n_arena;
-  if (hipMalloc((void **)&p->arena_dev, (size_t)n_arena * sizeof(float)) !=
-      hipSuccess) {
-    delete p;
+  if (hipMalloc((void **)&p->arena_dev, (size_t)n_arena * sizeof(float)) != hipSuccess)
     return fpl_fail(ctx, "fpl_program_create: arena allocation failed");
-  }
-  int rc = fpl_program_set_arena(p, arena, n_arena);
-  if (rc) {
-    hipFree(p->arena_dev);
-    delete p;
-    return rc;
-  }
-  *out = p;
+  FPL_TRY(fpl_program_set_arena(p.get(), arena, n_arena));
+  *out = p.release();
   return 0;
-}
+} FPL_CATCH(ctx)
 
 int fpl_program_set_arena(fpl_program *prog, const float *arena,
-                          int64_t n_arena) {
+                          int64_t n_arena) try {
   if (!prog || !arena) return fpl_fail(nullptr, "fpl_program_set_arena: NULL");
   fpl_ctx *ctx = prog->ctx;
   FPL_REQUIRE(ctx, n_arena == prog->n_arena,
@@ -287,9 +279,9 @@ int fpl_program_set_arena(fpl_program *prog, const float *arena,
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   prog->arena_version++;
   return 0;
-}
+} FPL_CATCH(prog ? prog->ctx : nullptr)
 
-int fpl_program_destroy(fpl_program *prog) {
+int fpl_program_destroy(fpl_program *prog) try {
   if (!prog) return 0;
   fpl_ctx *ctx = prog->ctx;
   hipSetDevice(ctx->device);
@@ -299,9 +291,9 @@ int fpl_program_destroy(fpl_program *prog) {
       prog->fast_state_h16_free[k](ctx, prog->fast_state_h16[k]);
   if (prog->fast_state_f32 && prog->fast_state_f32_free)
     prog->fast_state_f32_free(ctx, prog->fast_state_f32);
-  hipFree(prog->arena_dev);
+  hipFree(prog->arena_dev);   // null when fpl_program_create failed to allocate it: hipFree(nullptr) succeeds
   delete prog;
   return 0;
-}
+} FPL_CATCH(prog ? prog->ctx : nullptr)
 
 }  // extern "C"

@@ -118,7 +118,7 @@ extern "C" {
 int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
                         int in_mem, int32_t n, const int32_t in_dims[3],
                         int precision, float *out, int out_mem,
-                        int32_t out_dims[4]) {
+                        int32_t out_dims[4]) try {
   if (!ctx || !prog || !in || !in_dims)
     return fpl_fail(ctx, "fpl_program_forward: NULL argument");
   FPL_REQUIRE(ctx, n > 0, "fpl_program_forward: batch %d", n);
@@ -178,7 +178,7 @@ int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
                                 hipMemcpyDeviceToHost, ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 }  // extern "C"
 
@@ -466,7 +466,7 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
                      int src_dtype, int src_mem, float mean, float sd,
                      const int64_t dims[3], const int32_t tile_in[3],
                      const int32_t offset[3], int precision, int32_t z_begin,
-                     int32_t z_end, float *dst, int dst_mem) {
+                     int32_t z_end, float *dst, int dst_mem) try {
   if (!ctx || !prog || !src || !dims || !tile_in || !offset || !dst)
     return fpl_fail(ctx, "fpl_infer_volume: NULL argument");
   FPL_REQUIRE(ctx, src_dtype == FPL_U8 || src_dtype == FPL_F32,
@@ -524,17 +524,38 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
     std::mutex mu;
     std::condition_variable cv;
     std::deque<std::pair<int64_t, int64_t>> todo;
-    bool closed = false;
+    bool closed = false, cancel = false;                                    // cancel: the main loop is gone
     int32_t uploaded = src_mem == FPL_MEM_HOST ? 0 : G;                     // groups whose source rows are resident
     hipError_t copy_err = hipSuccess, up_err = hipSuccess;
     const int device = ctx->device;
-    std::thread uploader([&]() {
+    // joins the helpers on every way out of this branch (an early return, an exception, the second
+    // thread failing to start) - before `tmp` hands the staging buffers they use back to the cache
+    struct Helpers {
+      std::mutex &mu;
+      std::condition_variable &cv;
+      bool &closed, &cancel;
+      std::thread uploader, copier;
+      ~Helpers() {
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          closed = cancel = true;
+          cv.notify_all();
+        }
+        for (std::thread *t : {&uploader, &copier})
+          if (t->joinable()) t->join();
+      }
+    };
+    auto upload = [&]() {
       if (src_mem != FPL_MEM_HOST) return;
       hipStream_t us = nullptr;
       hipError_t e = hipSetDevice(device);
       if (e == hipSuccess) e = hipStreamCreateWithFlags(&us, hipStreamNonBlocking);
       int64_t have = rd_lo_t;
       for (int32_t g = 0; g < G; ++g) {
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          if (cancel) break;                  // nothing will read the remaining rows
+        }
         int32_t b, en;
         group(g, &b, &en);
         const int64_t need = read_hi(en);
@@ -551,8 +572,8 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
         cv.notify_all();
       }
       if (us) hipStreamDestroy(us);
-    });
-    std::thread copier([&]() {
+    };
+    auto copy_out = [&]() {
       hipStream_t cs = nullptr;
       hipError_t e = hipSetDevice(device);
       if (e == hipSuccess) e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
@@ -572,34 +593,32 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
       }
       if (cs) hipStreamDestroy(cs);
       copy_err = e;
-    });
+    };
     int rc = 0;
     *bits = 0u;
-    for (int32_t g = 0; g < G && rc == 0 && !*bits; ++g) {
-      int32_t b, e;
-      group(g, &b, &e);
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return uploaded > g; });
-        if (up_err != hipSuccess) break;
-      }
-      rc = infer_volume_impl(ctx, prog, vsrc, src_dtype, vsrc_mem, mean, sd, dims, tile_in, offset, prec, b, e,
-                             vdst, FPL_MEM_DEVICE, bits);
-      if (rc == 0 && !*bits) {
-        int64_t lo, hi;
-        rows(b, e, &lo, &hi);
-        std::lock_guard<std::mutex> lk(mu);
-        todo.emplace_back(lo, hi);
-        cv.notify_all();
-      }
-    }
     {
-      std::lock_guard<std::mutex> lk(mu);
-      closed = true;
-      cv.notify_all();
-    }
-    uploader.join();
-    copier.join();
+      Helpers helpers{mu, cv, closed, cancel};
+      helpers.uploader = std::thread(upload);
+      helpers.copier = std::thread(copy_out);
+      for (int32_t g = 0; g < G && rc == 0 && !*bits; ++g) {
+        int32_t b, e;
+        group(g, &b, &e);
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return uploaded > g; });
+          if (up_err != hipSuccess) break;
+        }
+        rc = infer_volume_impl(ctx, prog, vsrc, src_dtype, vsrc_mem, mean, sd, dims, tile_in, offset, prec, b, e,
+                               vdst, FPL_MEM_DEVICE, bits);
+        if (rc == 0 && !*bits) {
+          int64_t lo, hi;
+          rows(b, e, &lo, &hi);
+          std::lock_guard<std::mutex> lk(mu);
+          todo.emplace_back(lo, hi);
+          cv.notify_all();
+        }
+      }
+    }                                         // helpers joined
     if (rc == 0 && up_err != hipSuccess)
       return fpl_fail(ctx, "fpl_infer_volume: host-to-device copy: %s", hipGetErrorString(up_err));
     if (rc == 0 && copy_err != hipSuccess)
@@ -647,7 +666,7 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
                          "kernels (guard bits 0x%x): the result is not valid; use precision f32, or "
                          "'auto', which falls back to it", where(bits), bits);
   return rc;
-}
+} FPL_CATCH(ctx)
 
 const char *fpl_last_path(fpl_ctx *ctx) { return ctx ? ctx->last_path : ""; }
 

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void hist_u8(const uint8_t *__restrict__ src, 
 
 extern "C" int fpl_synth_substack_u8(fpl_ctx *ctx, uint64_t seed, const int64_t extent[3],
                                      const int64_t dims[3], const int64_t origin[3],
-                                     uint8_t *dst, int dst_mem) {
+                                     uint8_t *dst, int dst_mem) try {
   if (!ctx || !extent || !dims || !origin || !dst)
     return fpl_fail(ctx, "fpl_synth_substack_u8: NULL argument");
   for (int a = 0; a < 3; ++a)
@@ -202,10 +202,10 @@ extern "C" int fpl_synth_substack_u8(fpl_ctx *ctx, uint64_t seed, const int64_t 
     FPL_HIP(ctx, hipMemcpyAsync(dst, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 extern "C" int fpl_crop_substack_u8(fpl_ctx *ctx, const uint8_t *src, const int64_t extent[3],
-                                    const int64_t dims[3], const int64_t origin[3], uint8_t *dst) {
+                                    const int64_t dims[3], const int64_t origin[3], uint8_t *dst) try {
   if (!ctx || !src || !extent || !dims || !origin || !dst)
     return fpl_fail(ctx, "fpl_crop_substack_u8: NULL argument");
   for (int a = 0; a < 3; ++a)
@@ -226,10 +226,10 @@ extern "C" int fpl_crop_substack_u8(fpl_ctx *ctx, const uint8_t *src, const int6
   }
   FPL_HIP(ctx, hipGetLastError());
   return 0;                                     // stream-ordered: the consumers run on ctx->stream too
-}
+} FPL_CATCH(ctx)
 
 extern "C" int fpl_histogram_u8(fpl_ctx *ctx, const uint8_t *src, int src_mem, int64_t n,
-                                uint64_t out[256]) {
+                                uint64_t out[256]) try {
   if (!ctx || !src || !out) return fpl_fail(ctx, "fpl_histogram_u8: NULL argument");
   FPL_REQUIRE(ctx, n >= 0, "fpl_histogram_u8: n %lld", (long long)n);
   FPL_HIP(ctx, hipSetDevice(ctx->device));
@@ -255,11 +255,11 @@ extern "C" int fpl_histogram_u8(fpl_ctx *ctx, const uint8_t *src, int src_mem, i
   FPL_HIP(ctx, hipMemcpyAsync(out, hv, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 extern "C" int fpl_synth_volume_u8(fpl_ctx *ctx, uint64_t seed,
                                    const int64_t dims[3], const int64_t origin[3],
-                                   uint8_t *dst, int dst_mem) {
+                                   uint8_t *dst, int dst_mem) try {
   if (!ctx || !dims || !origin || !dst)
     return fpl_fail(ctx, "fpl_synth_volume_u8: NULL argument");
   for (int a = 0; a < 3; ++a)
@@ -289,4 +289,4 @@ extern "C" int fpl_synth_volume_u8(fpl_ctx *ctx, uint64_t seed,
     FPL_HIP(ctx, hipMemcpyAsync(dst, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)

@@ -872,7 +872,7 @@ extern "C" {
 int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
                        int32_t n_tensors, int32_t out_tensor, const float *weights,
                        int64_t n_weights, float lr, float beta1, float beta2,
-                       float eps, fpl_trainer **out) {
+                       float eps, fpl_trainer **out) try {
   if (!ctx || !layers || !weights || !out)
     return fpl_fail(ctx, "fpl_trainer_create: NULL argument");
   *out = nullptr;
@@ -902,7 +902,7 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
         for (int c = 0; c < L.cin; ++c) kind[L.w_off[q] + c] = 1;
     }
   }
-  fpl_trainer *t = new fpl_trainer();
+  std::unique_ptr<fpl_trainer, decltype(&fpl_trainer_destroy)> t(new fpl_trainer(), fpl_trainer_destroy);
   t->ctx = ctx;
   t->layers.assign(layers, layers + n_layers);
   t->n_tensors = n_tensors;
@@ -917,10 +917,7 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
             hipMalloc((void **)&t->kind, (size_t)n_weights) == hipSuccess &&
             hipMalloc((void **)&t->ones, 256 * sizeof(float)) == hipSuccess &&
             hipMalloc((void **)&t->zeros, 256 * sizeof(float)) == hipSuccess;
-  if (!ok) {
-    fpl_trainer_destroy(t);
-    return fpl_fail(ctx, "fpl_trainer_create: device allocation failed");
-  }
+  if (!ok) return fpl_fail(ctx, "fpl_trainer_create: device allocation failed");
   hipStream_t st = ctx->stream;
   FPL_HIP(ctx, hipMemcpyAsync(t->w, weights, nb, hipMemcpyHostToDevice, st));
   FPL_HIP(ctx, hipMemcpyAsync(t->kind, kind.data(), (size_t)n_weights, hipMemcpyHostToDevice, st));
@@ -930,11 +927,11 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
   FPL_HIP(ctx, hipMemsetAsync(t->zeros, 0, 256 * sizeof(float), st));
   fill_f32<<<1, 256, 0, st>>>(t->ones, 1.f, 256);
   FPL_HIP(ctx, hipStreamSynchronize(st));
-  *out = t;
+  *out = t.release();
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_trainer_destroy(fpl_trainer *t) {
+int fpl_trainer_destroy(fpl_trainer *t) try {
   if (!t) return 0;
   hipSetDevice(t->ctx->device);
   hipStreamSynchronize(t->ctx->stream);
@@ -943,14 +940,14 @@ int fpl_trainer_destroy(fpl_trainer *t) {
     if (p) hipFree(p);
   delete t;
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
-int fpl_trainer_grad_ptr(fpl_trainer *t, void **dev_ptr, int64_t *n_floats) {
+int fpl_trainer_grad_ptr(fpl_trainer *t, void **dev_ptr, int64_t *n_floats) try {
   if (!t || !dev_ptr || !n_floats) return fpl_fail(nullptr, "fpl_trainer_grad_ptr: NULL");
   *dev_ptr = t->g;
   *n_floats = t->n_w;
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 static int copy_arena(fpl_trainer *t, float *dev, float *host, int64_t n, bool to_host) {
   fpl_ctx *ctx = t->ctx;
@@ -964,61 +961,61 @@ static int copy_arena(fpl_trainer *t, float *dev, float *host, int64_t n, bool t
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
 }
-int fpl_trainer_get_weights(fpl_trainer *t, float *out, int64_t n) {
+int fpl_trainer_get_weights(fpl_trainer *t, float *out, int64_t n) try {
   if (!t || !out) return fpl_fail(nullptr, "fpl_trainer_get_weights: NULL");
   return copy_arena(t, t->w, out, n, true);
-}
-int fpl_trainer_get_grads(fpl_trainer *t, float *out, int64_t n) {
+} FPL_CATCH(t ? t->ctx : nullptr)
+int fpl_trainer_get_grads(fpl_trainer *t, float *out, int64_t n) try {
   if (!t || !out) return fpl_fail(nullptr, "fpl_trainer_get_grads: NULL");
   return copy_arena(t, t->g, out, n, true);
-}
-int fpl_trainer_set_weights(fpl_trainer *t, const float *w, int64_t n) {
+} FPL_CATCH(t ? t->ctx : nullptr)
+int fpl_trainer_set_weights(fpl_trainer *t, const float *w, int64_t n) try {
   if (!t || !w) return fpl_fail(nullptr, "fpl_trainer_set_weights: NULL");
   return copy_arena(t, t->w, const_cast<float *>(w), n, false);
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 // Adam state: first / second moments in the weight arena's layout (moving-statistics slots
 // unused) and the number of updates applied - what Keras' model.save keeps as
 // `optimizer_weights` (flypylib/fplnetwork.py:15-17,81-97 save through it)
-int fpl_trainer_get_opt_state(fpl_trainer *t, float *m, float *v, int64_t n, int64_t *steps) {
+int fpl_trainer_get_opt_state(fpl_trainer *t, float *m, float *v, int64_t n, int64_t *steps) try {
   if (!t || !m || !v || !steps) return fpl_fail(nullptr, "fpl_trainer_get_opt_state: NULL");
   FPL_TRY(copy_arena(t, t->m, m, n, true));
   FPL_TRY(copy_arena(t, t->v, v, n, true));
   *steps = t->step_count;
   return 0;
-}
-int fpl_trainer_set_opt_state(fpl_trainer *t, const float *m, const float *v, int64_t n, int64_t steps) {
+} FPL_CATCH(t ? t->ctx : nullptr)
+int fpl_trainer_set_opt_state(fpl_trainer *t, const float *m, const float *v, int64_t n, int64_t steps) try {
   if (!t || !m || !v) return fpl_fail(nullptr, "fpl_trainer_set_opt_state: NULL");
   if (steps < 0) return fpl_fail(t->ctx, "fpl_trainer_set_opt_state: %lld steps", (long long)steps);
   FPL_TRY(copy_arena(t, t->m, const_cast<float *>(m), n, false));
   FPL_TRY(copy_arena(t, t->v, const_cast<float *>(v), n, false));
   t->step_count = steps;
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
-int fpl_trainer_set_grads(fpl_trainer *t, const float *g, int64_t n) {
+int fpl_trainer_set_grads(fpl_trainer *t, const float *g, int64_t n) try {
   if (!t || !g) return fpl_fail(nullptr, "fpl_trainer_set_grads: NULL");
   return copy_arena(t, t->g, const_cast<float *>(g), n, false);
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 // one RCCL all-reduce (sum) of the flat gradient arena on the context's stream; the
 // Adam kernel of fpl_trainer_apply is ordered behind it on the same stream
-int fpl_allreduce_grads(fpl_trainer *t) {
+int fpl_allreduce_grads(fpl_trainer *t) try {
   if (!t) return fpl_fail(nullptr, "fpl_allreduce_grads: NULL");
   return fpl_comm_allreduce_sum_f32(t->ctx, t->g, t->n_w);
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 // every rank starts from rank `root`'s weights and Adam state
-int fpl_trainer_broadcast_state(fpl_trainer *t, int32_t root) {
+int fpl_trainer_broadcast_state(fpl_trainer *t, int32_t root) try {
   if (!t) return fpl_fail(nullptr, "fpl_trainer_broadcast_state: NULL");
   FPL_TRY(fpl_comm_broadcast_f32(t->ctx, t->w, t->n_w, root));
   FPL_TRY(fpl_comm_broadcast_f32(t->ctx, t->m, t->n_w, root));
   FPL_TRY(fpl_comm_broadcast_f32(t->ctx, t->v, t->n_w, root));
   FPL_HIP(t->ctx, hipStreamSynchronize(t->ctx->stream));
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
-int fpl_trainer_apply(fpl_trainer *t, float grad_scale) {
+int fpl_trainer_apply(fpl_trainer *t, float grad_scale) try {
   if (!t) return fpl_fail(nullptr, "fpl_trainer_apply: NULL");
   fpl_ctx *ctx = t->ctx;
   FPL_HIP(ctx, hipSetDevice(ctx->device));
@@ -1033,12 +1030,12 @@ int fpl_trainer_apply(fpl_trainer *t, float grad_scale) {
   }
   FPL_HIP(ctx, hipGetLastError());
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
                      const uint8_t *labels, int labels_mem, int32_t batch,
                      const int32_t patch[3], uint64_t seed, float *loss,
-                     float *accuracy) {
+                     float *accuracy) try {
   if (!t || !data || !labels || !patch) return fpl_fail(nullptr, "fpl_trainer_step: NULL");
   fpl_ctx *ctx = t->ctx;
   FPL_REQUIRE(ctx, batch > 0, "fpl_trainer_step: batch %d", batch);
@@ -1667,20 +1664,20 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   if (loss) *loss = (float)(hs[0] / (double)n_out);
   if (accuracy) *accuracy = (float)(hs[1] / (double)n_out);
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
-int fpl_trainer_set_loss(fpl_trainer *t, int loss_kind) {
+int fpl_trainer_set_loss(fpl_trainer *t, int loss_kind) try {
   if (!t) return fpl_fail(nullptr, "fpl_trainer_set_loss: trainer is NULL");
   FPL_REQUIRE(t->ctx, loss_kind >= FPL_LOSS_BCE && loss_kind <= FPL_LOSS_MASKED_FOCAL,
               "fpl_trainer_set_loss: unknown loss %d", loss_kind);
   t->loss_kind = loss_kind;
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
-int fpl_trainer_metric_sums(fpl_trainer *t, double out[FPL_N_METRIC_SUMS]) {
+int fpl_trainer_metric_sums(fpl_trainer *t, double out[FPL_N_METRIC_SUMS]) try {
   if (!t || !out) return fpl_fail(nullptr, "fpl_trainer_metric_sums: NULL argument");
   memcpy(out, t->last_sums, sizeof(t->last_sums));
   return 0;
-}
+} FPL_CATCH(t ? t->ctx : nullptr)
 
 }  // extern "C"

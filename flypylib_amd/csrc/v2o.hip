@@ -1448,7 +1448,7 @@ extern "C" {
 int fpl_v2o_smooth(fpl_ctx *ctx, const float *pred, int pred_mem,
                    const int64_t dims[3], int32_t r, const double *weights,
                    int32_t wr, const int64_t *ranks, int32_t n_ranks,
-                   float *rank_values) {
+                   float *rank_values) try {
   if (!ctx || !pred || !dims || !weights)
     return fpl_fail(ctx, "fpl_v2o_smooth: NULL argument");
   FPL_REQUIRE(ctx, r >= 0 && wr >= 0, "fpl_v2o_smooth: negative radius");
@@ -1563,16 +1563,16 @@ int fpl_v2o_smooth(fpl_ctx *ctx, const float *pred, int pred_mem,
   FPL_HIP(ctx, hipStreamSynchronize(st));
   S.valid = true;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_set_floor(fpl_ctx *ctx, float floor) {
+int fpl_v2o_set_floor(fpl_ctx *ctx, float floor) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_v2o_set_floor: ctx is NULL");
   FPL_REQUIRE(ctx, floor == floor, "fpl_v2o_set_floor: NaN");
   ctx->v2o.floor = floor;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_copy_smoothed(fpl_ctx *ctx, float *dst, int dst_mem) {
+int fpl_v2o_copy_smoothed(fpl_ctx *ctx, float *dst, int dst_mem) try {
   if (!ctx || !dst) return fpl_fail(ctx, "fpl_v2o_copy_smoothed: NULL argument");
   FPL_REQUIRE(ctx, ctx->v2o.valid, "fpl_v2o_copy_smoothed: no smoothed volume");
   const V2oState &S = ctx->v2o;
@@ -1583,7 +1583,7 @@ int fpl_v2o_copy_smoothed(fpl_ctx *ctx, float *dst, int dst_mem) {
                               ctx->stream));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
                    int64_t *n_out, int32_t *n_rounds, bool use_seg, int seg_dilate,
@@ -1762,12 +1762,12 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
 
 
 int fpl_v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
-                int64_t *n_out, int32_t *n_rounds) {
+                int64_t *n_out, int32_t *n_rounds) try {
   return v2o_nms(ctx, thresh, out_zyxv, cap, n_out, n_rounds, false, 0, 0);
-}
+} FPL_CATCH(ctx)
 
 int fpl_v2o_nms_seg(fpl_ctx *ctx, double thresh, int32_t seg_dilate, int32_t seg_force,
-                    double *out_zyxv, int64_t cap, int64_t *n_out, int32_t *n_rounds) {
+                    double *out_zyxv, int64_t cap, int64_t *n_out, int32_t *n_rounds) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_v2o_nms_seg: ctx is NULL");
   FPL_REQUIRE(ctx, ctx->v2o.valid && ctx->v2o.seg_valid,
               "fpl_v2o_nms_seg: call fpl_v2o_smooth and fpl_v2o_set_seg first");
@@ -1785,10 +1785,10 @@ int fpl_v2o_nms_seg(fpl_ctx *ctx, double thresh, int32_t seg_dilate, int32_t seg
     attr_set[ctx->device % FPL_MAX_DEVICES] = true;
   }
   return v2o_nms(ctx, thresh, out_zyxv, cap, n_out, n_rounds, true, seg_dilate, seg_force);
-}
+} FPL_CATCH(ctx)
 
 int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_mem,
-                    const int64_t dims[3], int64_t sz_thd) {
+                    const int64_t dims[3], int64_t sz_thd) try {
   if (!ctx || !seg || !dims) return fpl_fail(ctx, "fpl_v2o_set_seg: NULL argument");
   V2oState &S = ctx->v2o;
   FPL_REQUIRE(ctx, S.valid, "fpl_v2o_set_seg: call fpl_v2o_smooth first");
@@ -1868,9 +1868,9 @@ int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_me
   FPL_HIP(ctx, hipStreamSynchronize(st));
   S.seg_valid = true;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_select(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, float *rank_values) {
+int fpl_v2o_select(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, float *rank_values) try {
   if (!ctx || !ranks || !rank_values) return fpl_fail(ctx, "fpl_v2o_select: NULL argument");
   const V2oState &S = ctx->v2o;
   FPL_REQUIRE(ctx, S.valid, "fpl_v2o_select: call fpl_v2o_smooth first");
@@ -1888,6 +1888,6 @@ int fpl_v2o_select(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, float *r
     FPL_TRY(v2o_select(ctx, S, n_pad, ranks, n_ranks, rank_values, hist_dev, (float *)p, false, tmp));
   FPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 }  // extern "C"

@@ -131,7 +131,7 @@ int grow(fpl_ctx *ctx, void **p, size_t *cap, size_t need) {
 extern "C" {
 
 int fpl_v2o_smooth_f64(fpl_ctx *ctx, const double *pred, int pred_mem, const int64_t dims[3],
-                       int32_t r, const double *weights, int32_t wr) {
+                       int32_t r, const double *weights, int32_t wr) try {
   // integer mode (fpl_v2o_set_integer) holds for ONE call: taken and cleared before anything
   // below can fail, so that a failed call never leaves it set for the next float64 volume
   int tr = 0;
@@ -209,15 +209,15 @@ int fpl_v2o_smooth_f64(fpl_ctx *ctx, const double *pred, int pred_mem, const int
   S.f64 = true;
   S.valid = true;          // dims and radius are set; `smoothed` is filled by fpl_v2o_rank_f64
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_set_integer(fpl_ctx *ctx, int32_t on) {
+int fpl_v2o_set_integer(fpl_ctx *ctx, int32_t on) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_v2o_set_integer: ctx is NULL");
   ctx->v2o.trunc_passes = on != 0;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_select_f64(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, double *rank_values) {
+int fpl_v2o_select_f64(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, double *rank_values) try {
   if (!ctx || (n_ranks > 0 && (!ranks || !rank_values)))
     return fpl_fail(ctx, "fpl_v2o_select_f64: NULL argument");
   V2oState &S = ctx->v2o;
@@ -266,9 +266,9 @@ int fpl_v2o_select_f64(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, doub
   FPL_HIP(ctx, hipStreamSynchronize(st));
   S.sorted = true;
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_rank_f64(fpl_ctx *ctx, double thresh, int64_t *n_candidates) {
+int fpl_v2o_rank_f64(fpl_ctx *ctx, double thresh, int64_t *n_candidates) try {
   if (!ctx) return fpl_fail(nullptr, "fpl_v2o_rank_f64: ctx is NULL");
   V2oState &S = ctx->v2o;
   FPL_REQUIRE(ctx, S.valid && S.f64 && S.sorted,
@@ -317,9 +317,9 @@ int fpl_v2o_rank_f64(fpl_ctx *ctx, double thresh, int64_t *n_candidates) {
   }
   FPL_HIP(ctx, hipStreamSynchronize(st));
   return 0;
-}
+} FPL_CATCH(ctx)
 
-int fpl_v2o_values_f64(fpl_ctx *ctx, const int64_t *flat, int64_t n, double *out) {
+int fpl_v2o_values_f64(fpl_ctx *ctx, const int64_t *flat, int64_t n, double *out) try {
   if (!ctx || (n > 0 && (!flat || !out))) return fpl_fail(ctx, "fpl_v2o_values_f64: NULL argument");
   V2oState &S = ctx->v2o;
   FPL_REQUIRE(ctx, S.f64 && S.smoothed64, "fpl_v2o_values_f64: no float64 volume");
@@ -340,6 +340,6 @@ int fpl_v2o_values_f64(fpl_ctx *ctx, const int64_t *flat, int64_t n, double *out
   FPL_HIP(ctx, hipMemcpyAsync(out, o_dev, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   FPL_HIP(ctx, hipStreamSynchronize(st));
   return 0;
-}
+} FPL_CATCH(ctx)
 
 }  // extern "C"

@@ -9,9 +9,12 @@
  * flypylib_amd/_capi.py and INTEGRATION.md.
  *
  * Conventions
- *   - every function returns 0 on success, non-zero on failure; the message is
- *     available from fpl_last_error(ctx) (ctx may be NULL for create failures).
- *   - no exceptions / abort across the boundary.
+ *   - every function but fpl_abi_version, fpl_last_error and fpl_last_path returns
+ *     0 on success and non-zero on any host-side failure, exhaustion of host
+ *     memory included; the message is available from fpl_last_error(ctx) (ctx
+ *     may be NULL: the calling thread's last message, e.g. of a failed create).
+ *     No C++ exception or abort crosses the boundary, and a failed create leaves
+ *     *out NULL and nothing allocated.
  *   - host buffers are caller-owned, C-contiguous.  Pointers tagged
  *     `mem = FPL_MEM_DEVICE` are device pointers of the same HIP device/primary
  *     context (e.g. a torch tensor's data_ptr()).
@@ -49,8 +52,10 @@ enum fpl_dtype { FPL_U8 = 0, FPL_F32 = 1, FPL_F64 = 2 };
  * three MFMAs per product: probabilities within ~4e-6 of fp32 - inside the reference's
  * 1e-3 gate, the same detected point set as the fp32 path's, order included up to
  * confidences that tie to 1e-6 - at a third of the 16-bit rate).  Split kernels exist for
- * vgg_like, vgg_like2 (stride-4 lattices) and unet_like / unet_like2 / unet_like3 /
- * unet_like4 (cubic tiles); other graphs are refused at FPL_PREC_F16S.  Its operands are
+ * vgg_like, vgg_like2 (stride-4 lattices), the U-Net skeletons unet_like / unet_like2 /
+ * unet_like3 / unet_like4 and, through the layer-by-layer graph executor, baseline_model,
+ * resnet_like, unet_like4b and unet_like_vol (cubic tiles); a layer program that no 16-bit
+ * executor has kernels for is refused at FPL_PREC_F16S / F16 / BF16.  Its operands are
  * IEEE halves: a folded weight, a normalised input voxel or an activation beyond 65504
  * makes the call FAIL (the kernels check every value they split) - never a wrong result. */
 enum fpl_precision {

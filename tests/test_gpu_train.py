@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from flypylib_amd import _capi, fplmodels, synth
-from flypylib_amd.program import LayerGraph
+from flypylib_amd.program import L_CONV, LayerGraph
 from oracle import train_oracle
 
 pytestmark = pytest.mark.gpu
@@ -401,6 +401,34 @@ def test_training_reduces_loss(ctx):
         tr.apply(1.0)
         first = loss if first is None else first
     assert loss < 0.7 * first
+
+
+def test_trainer_create_reports_host_allocation_failure(ctx):
+    """a host allocation that fails inside the C ABI (fpl_trainer_create's per-weight table for an
+    arena of 2^60 floats, made before any device work) returns an error with a message instead of
+    taking the process down (include/fplhip.h: no exception crosses the boundary); *out is NULL and
+    the context trains as before"""
+    import ctypes as C
+    layer = (_capi.fpl_layer * 1)()
+    # one 1x1x1 conv, 1 -> 1 channel, tensor 0 -> 1, no bias, no activation, kernel at offset 0
+    layer[0] = _capi.fpl_layer(L_CONV, 0, -1, 1, 1, 1, 1, 0, 0, 0.0,
+                               (C.c_int32 * 6)(), (C.c_int64 * 4)(0, 0, 0, 0))
+    w = np.zeros(1, np.float32)
+    out = C.c_void_p(0x10)
+    rc = ctx.lib.fpl_trainer_create(ctx.h, layer, 1, 2, 1, w.ctypes.data, 1 << 60,
+                                    1e-3, 0.9, 0.999, 1e-8, C.byref(out))
+    msg = ctx.lib.fpl_last_error(ctx.h).decode()
+    assert rc != 0
+    assert 'fpl_trainer_create' in msg and 'out of host memory' in msg, msg
+    assert out.value is None
+    g = fplmodels.vgg_like()[0]
+    tr = _capi.Trainer(ctx, g)
+    rng = np.random.default_rng(6)
+    data = rng.standard_normal((2, 18, 18, 18, 1)).astype(np.float32)
+    labels = (rng.random((2, 1, 1, 1, 1)) > 0.5).astype(np.uint8)
+    loss, _ = tr.step(data, labels, seed=1)
+    assert np.isfinite(loss) and loss > 0
+    tr.close()
 
 
 def test_fplnetwork_train_api_end_to_end(ctx, tmp_path):

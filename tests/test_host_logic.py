@@ -44,6 +44,61 @@ def test_library_exports_nothing_but_the_declared_c_abi():
     assert exported == declared, (sorted(exported - declared)[:5], sorted(declared - exported)[:5])
 
 
+def _closing_brace(src, i):
+    """index of the '}' that closes the '{' at src[i] (comments and literals skipped)"""
+    depth = 0
+    while True:
+        if src.startswith('//', i):
+            i = src.index('\n', i)
+        elif src.startswith('/*', i):
+            i = src.index('*/', i) + 1
+        elif src[i] in '"\'':
+            q, i = src[i], i + 1
+            while src[i] != q:
+                i += 2 if src[i] == '\\' else 1
+        elif src[i] == '{':
+            depth += 1
+        elif src[i] == '}':
+            depth -= 1
+            if depth == 0:
+                return i
+        i += 1
+
+
+def test_every_c_abi_entry_point_is_guarded():
+    """no C++ exception crosses the C ABI (fplhip.h): every entry point is a function-try-block
+    whose handler is FPL_CATCH (csrc/common.h), but for the three that neither allocate nor call
+    anything that can throw; and the only threads started by hand are the pipeline helpers of
+    infer.hip, which a scope object joins on every way out"""
+    csrc = os.path.join(ROOT, 'flypylib_amd', 'csrc')
+    hdr = open(os.path.join(ROOT, 'include', 'fplhip.h')).read()
+    declared = set(re.findall(r'\b(fpl_[a-z0-9_]+)\s*\(', hdr))
+    exempt = {'fpl_abi_version', 'fpl_last_error', 'fpl_last_path'}
+    assert exempt <= declared
+    srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+            if f.endswith(('.hip', '.h'))}
+    guarded = 0
+    for name in sorted(declared - exempt):
+        defs = [(f, m) for f, s in srcs.items() if f.endswith('.hip')
+                for m in re.finditer(r'^(?:extern "C" )?int ' + name + r'\(', s, re.M)]
+        assert len(defs) == 1, (name, [f for f, _ in defs])
+        f, m = defs[0]
+        s = srcs[f]
+        depth, i = 0, m.end() - 1
+        while True:                                  # the ')' that closes the parameter list
+            depth += {'(': 1, ')': -1}.get(s[i], 0)
+            if depth == 0:
+                break
+            i += 1
+        assert s.startswith(') try {', i), '%s (%s) is not a function-try-block' % (name, f)
+        end = _closing_brace(s, i + len(') try '))
+        assert s.startswith(' FPL_CATCH(', end + 1), '%s (%s): no FPL_CATCH after its body' % (name, f)
+        guarded += 1
+    assert guarded == len(declared) - len(exempt) == 55
+    threads = [f for f, s in srcs.items() if 'std::thread' in s]
+    assert threads == ['infer.hip'], threads
+
+
 def test_fpl_op_struct_layout_matches_header():
     # int32 x8, int64 x3, int32 x6 -> 80 bytes with natural alignment
     assert ctypes.sizeof(_capi.fpl_op) == 80
