@@ -144,6 +144,7 @@ struct StemSArgs {
   const float *shift1, *shift2;
   x8::Tensor p1;           // chunk-local pool-1 tensor (planes of 8-channel passes, vgg_split_lds.h)
   int nbx, nby, nbz;       // blocks of S_PX x S_PY x S_PZ pooled voxels
+  int trim;                // partial blocks run only the tasks that hold P1 voxels (StemTrim)
   // half-range guard (mfma_util.h): conv3 1->48's outputs are bounded on the host from
   // sum |w| and the input limit (uint8: |u - c0| <= 255; float volumes: |x| <= xlim, checked
   // per loaded voxel), conv1's pooled outputs are checked where they are split for the store
@@ -290,6 +291,37 @@ __device__ __forceinline__ void stem_store_edge(const StemSArgs &a, unsigned sho
     *reinterpret_cast<unsigned *>(&tile[S_TILE + row * S_TP + 64]) = (v0 >> 16) | (v1 & 0xFFFF0000u);
 }
 
+// A block that P1 cuts (the last block column, row or layer: at 520^3 4 of its 32 pooled x, 4 of
+// its 8 y) runs only the tasks that hold P1 voxels.  Its tasks are patches of PXW x (16 / PXW)
+// pooled (x, y) at one z - lane c at x c % PXW, y c / PXW - so that 4 live x fill a task's 16
+// lanes as 4 x 4 patches.  A lane's voxel enters conv3 only through Geo::base (the tap offsets
+// are relative) and the store address, so every voxel keeps its exact sequence of MFMAs.  Tasks
+// go to waves as in a full block (task w + 8 ti), x patch fastest, then y, then z.  (The 4 x 4
+// patches read the tile 4-way bank-conflicted - a row is 16 banks from the next - which their 8x
+// fewer stages pay for.)
+struct StemTrim {
+  int pxs;                 // log2 PXW (2, 3 or 4)
+  int ntx, nty;            // patches along x (1 or 2) and y (1 .. 8)
+  int nt;                  // live tasks of the block
+  int mag;                 // r / nty as (r * mag) >> 10, exact for r < 64
+};
+
+__device__ __forceinline__ StemTrim stem_trim(const StemSArgs &a, const StemBlock &b) {
+  StemTrim t;
+  const int lx = min(S_PX, a.p1.X - b.px0), ly = min(S_PY, a.p1.Y - b.py0), lz = min(S_PZ, a.p1.Z - b.pz0);
+  t.pxs = lx > 8 ? 4 : lx > 4 ? 3 : 2;
+  const int pyh = 16 >> t.pxs;
+  t.ntx = (lx + (1 << t.pxs) - 1) >> t.pxs;
+  t.nty = (ly + pyh - 1) / pyh;
+  t.nt = lz * t.nty * t.ntx;
+  t.mag = (1024 + t.nty - 1) / t.nty;
+  return t;
+}
+
+__device__ __forceinline__ bool stem_full(const StemSArgs &a, const StemBlock &b) {
+  return b.px0 + S_PX <= a.p1.X && b.py0 + S_PY <= a.p1.Y && b.pz0 + S_PZ <= a.p1.Z;
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
 template <typename SRC>
@@ -416,7 +448,7 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
   struct Gin {                          // the taps conv3 of one sub-step reads from the LDS tile
     unsigned p[INT ? 1 : 2][3], s0[INT ? 1 : 2], s1[INT ? 1 : 2];
   };
-  struct Geo { int base, xrel, yrel, zrel, pzl, pyl, xh; };
+  struct Geo { int base, xrel, yrel, zrel, pzl, pyl, pxl; bool live; };   // (trimmed blocks: pyl per lane)
   int cur = 0;
   for (;;) {
     const int qn = q + G;
@@ -432,10 +464,30 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
       Geo t;
       const int task = wave + S_WAVES * ti;
       const int row = task >> 1;
-      t.xh = task & 1; t.pzl = row / S_PY; t.pyl = row % S_PY;
-      t.base = 2 * (((2 * t.pzl) * S_TY + 2 * t.pyl) * S_TP + 2 * (16 * t.xh + c));
+      const int xh = task & 1;
+      t.pzl = row / S_PY; t.pyl = row % S_PY; t.pxl = 16 * xh + c; t.live = true;
+      t.base = 2 * (((2 * t.pzl) * S_TY + 2 * t.pyl) * S_TP + 2 * (16 * xh + c));
       // INT: planes of padding in the 3 x 3 x 3 window of this lane's outputs (0 inside)
-      t.xrel = (int)(blk.gx0 + 2 * (16 * t.xh + c) + 3 - a.SX);
+      t.xrel = (int)(blk.gx0 + 2 * (16 * xh + c) + 3 - a.SX);
+      t.yrel = (int)(blk.gy0 + 2 * t.pyl + 3 - a.SY);
+      t.zrel = (int)(blk.gz0 + 2 * t.pzl + 3 - a.z_hi);
+      return t;
+    };
+    // a trimmed block's task (StemTrim); a wave's tasks past the live ones repeat the last live
+    // task with its store masked
+    const StemTrim trm = stem_trim(a, blk);
+    auto geo_trim = [&](int ti) {
+      Geo t;
+      int task = wave + S_WAVES * ti;
+      t.live = task < trm.nt;
+      task = t.live ? task : trm.nt - 1;
+      const int r = task >> (trm.ntx - 1), tx = task & (trm.ntx - 1);
+      const int tz = (r * trm.mag) >> 10, ty = r - tz * trm.nty;
+      t.pzl = tz;
+      t.pyl = (ty << (4 - trm.pxs)) + (c >> trm.pxs);
+      t.pxl = (tx << trm.pxs) + (c & ((1 << trm.pxs) - 1));
+      t.base = 2 * (((2 * t.pzl) * S_TY + 2 * t.pyl) * S_TP + 2 * t.pxl);
+      t.xrel = (int)(blk.gx0 + 2 * t.pxl + 3 - a.SX);
       t.yrel = (int)(blk.gy0 + 2 * t.pyl + 3 - a.SY);
       t.zrel = (int)(blk.gz0 + 2 * t.pzl + 3 - a.z_hi);
       return t;
@@ -445,8 +497,14 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
     // table - so its pass is compiled without the three 16-B table reads per sub-step
     const bool interior = INT && blk.gx0 + 2 * S_PX + 2 <= a.SX && blk.gy0 + 2 * S_PY + 2 <= a.SY &&
                           blk.gz0 + 2 * S_PZ + 2 <= a.z_hi;
-    auto block_pass = [&](auto edge_t) {
-      constexpr bool EDGE = decltype(edge_t)::value;
+    auto block_pass = [&](auto edge_t, auto trim_t) {
+      constexpr bool EDGE = decltype(edge_t)::value, TRIM = decltype(trim_t)::value;
+      auto gg = [&](int ti) {
+        if constexpr (TRIM) return geo_trim(ti);
+        else return geo(ti);
+      };
+      // this wave's tasks (at least one: a wave without a live task runs a masked one)
+      const int ntask = TRIM ? max(1, (trm.nt - wave + S_WAVES - 1) / S_WAVES) : S_TASKS;
       f32x4 kin[3];
       if (INT && !EDGE) {
 #pragma unroll
@@ -504,7 +562,7 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
 #pragma unroll
         for (int b = 0; b < 3; ++b) a2[e][b] = f32x4{0.f, 0.f, 0.f, 0.f};
       {                                   // prime: conv3 of (task 0, sub-step 0), reads of sub-step 1
-        const Geo t0 = geo(0);
+        const Geo t0 = gg(0);
         gather(t0, 0, Gd[0]);
         gather_init(t0, 0, gin);
         const h16x8 bh = frag(Gd[0], 0), bl = INT ? bh : frag(Gd[0], INT ? 0 : 1);
@@ -515,7 +573,7 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
         for (int q = 1; q < DEPTH; ++q) gather(t0, q, Gd[q % NGB]);
       }
 #pragma unroll 1
-      for (int ti = 0; ti < S_TASKS; ++ti) {
+      for (int ti = 0; ti < ntask; ++ti) {
         // The next block's tile arrives in S_TASKS groups of S_RPT rows, three tasks per group:
         // group ti + 2 is LOADED at the end of this task; group ti + 1 (loaded a task ago, `rr`)
         // is CONVERTED late in this task; group ti (`hb`) is WRITTEN to the idle tile buffer in
@@ -527,7 +585,7 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
         const SRC *lbase = load2 ? base_2 : base_n;
         const unsigned ltab = load2 ? tab_2 : tab_n, lxc = load2 ? nx2.xc : nxt.xc;
         const int lidx = S_RPT * ((ti + 2) & (S_TASKS - 1));
-        const Geo tg = geo(ti), tn = geo((ti + 1) & (S_TASKS - 1)), tp = geo((ti + S_TASKS - 1) & (S_TASKS - 1));
+        const Geo tg = gg(ti), tn = gg((ti + 1) & (S_TASKS - 1)), tp = gg((ti + S_TASKS - 1) & (S_TASKS - 1));
 #pragma unroll
         for (int sub = 0; sub < 8; ++sub) {
           const int sp = sub >> 1, e = sub & 1, en = e ^ 1;
@@ -587,12 +645,12 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
           for (int i = 9; i < 15; ++i) c1(i);
           if (sub == 0) {
             // the previous task's pooled voxel (its last pair was pooled in the slots above)
-            const int pz = blk.pz0 + tp.pzl, py = blk.py0 + tp.pyl, px = blk.px0 + 16 * tp.xh + c;
+            const int pz = blk.pz0 + tp.pzl, py = blk.py0 + tp.pyl, px = blk.px0 + tp.pxl;
             f32x4 pv[3];
 #pragma unroll
             for (int b = 0; b < 3; ++b) pv[b] = poolf[b] + sh2g[b];
             x8::store12_sel(a.p1, a.p1.vox(pz, py, px), g, pv, ovf,
-                            ti > 0 && pz < a.p1.Z && py < a.p1.Y && px < a.p1.X, a.dump);
+                            ti > 0 && tp.live && pz < a.p1.Z && py < a.p1.Y && px < a.p1.X, a.dump);
 #pragma unroll
             for (int b = 0; b < 3; ++b) poolf[b] = sh2n[b];                       // (the ReLU)
           }
@@ -613,22 +671,50 @@ __global__ __launch_bounds__(64 * S_WAVES, 2) void vggs_stem_pool(StemSArgs a) {
         }
       }
       {                                   // drain: the last task's last pair and its store
-        const Geo t7 = geo(S_TASKS - 1);
+        const Geo t7 = gg(ntask - 1);
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             poolf[b][r] = __builtin_fmaxf(__builtin_fmaxf(poolf[b][r], a2[0][b][r]), a2[1][b][r]);
-        const int pz = blk.pz0 + t7.pzl, py = blk.py0 + t7.pyl, px = blk.px0 + 16 * t7.xh + c;
+        const int pz = blk.pz0 + t7.pzl, py = blk.py0 + t7.pyl, px = blk.px0 + t7.pxl;
         f32x4 pv[3];
 #pragma unroll
         for (int b = 0; b < 3; ++b) pv[b] = poolf[b] + sh2g[b];
         x8::store12_sel(a.p1, a.p1.vox(pz, py, px), g, pv, ovf,
-                        pz < a.p1.Z && py < a.p1.Y && px < a.p1.X, a.dump);
+                        t7.live && pz < a.p1.Z && py < a.p1.Y && px < a.p1.X, a.dump);
+      }
+      if (TRIM && ntask < S_TASKS) {
+        // The fill of the next tile that the tasks left out would have carried: group ntask is
+        // converted (hb), groups ntask + 1 .. 7 are loaded here in one batch (float rows: two);
+        // then groups 0 and 1 of the block after next, as a full block's last task leaves them in
+        // hb and rr.
+        stem_write_rows<!INT>(tnext, wrow0, S_RPT * ntask, lane, hb);
+        constexpr int FB = INT ? S_TASKS - 1 : 4;     // groups loaded at once (float rows: registers)
+        StemRows<SRC> f8;
+        stem_load_rows<SRC>(base_2, tab_2, nx2.xc, 0, f8);
+        stem_load_rows<SRC>(base_2, tab_2, nx2.xc, S_RPT, rr);
+#pragma unroll
+        for (int j0 = 0; j0 < S_TASKS - 1; j0 += FB) {
+          StemRows<SRC> fr[FB];
+#pragma unroll
+          for (int j = 0; j < FB; ++j)
+            if (j0 + j < S_TASKS - 1 && ntask + 1 + j0 + j < S_TASKS)
+              stem_load_rows<SRC>(base_n, tab_n, nxt.xc, S_RPT * (ntask + 1 + j0 + j), fr[j]);
+#pragma unroll
+          for (int j = 0; j < FB; ++j)
+            if (j0 + j < S_TASKS - 1 && ntask + 1 + j0 + j < S_TASKS) {
+              StemBits fb;
+              stem_convert_rows<SRC>(a, nxt, lut, fr[j], fb, xmax);
+              stem_write_rows<!INT>(tnext, wrow0, S_RPT * (ntask + 1 + j0 + j), lane, fb);
+            }
+        }
+        stem_convert_rows<SRC>(a, nx2, lut, f8, hb, xmax);
       }
     };
-    if (interior) block_pass(std::false_type{});
-    else block_pass(std::true_type{});
+    if (a.trim && !stem_full(a, blk)) block_pass(std::true_type{}, std::true_type{});
+    else if (interior) block_pass(std::false_type{}, std::false_type{});
+    else block_pass(std::true_type{}, std::false_type{});
     if (!has_next) break;
     stem_store_edge<SRC>(a, tnext, lut, wrow0, lane, ee, xmax);
     stem_load_edge<SRC>(a, nx2, wrow0, lane, ee);
@@ -1721,6 +1807,10 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
   int64_t cz_chunk = std::max<int64_t>(4, (budget / p1_row_bytes - 6) / 2);
   cz_chunk = std::min<int64_t>(cz_chunk, cz_hi - cz_lo);
   cz_chunk = (cz_chunk + 3) / 4 * 4;
+  // FPL_VGG_EDGE_BLOCKS=0: the stem walks its partial blocks in full, as every block (same
+  // results, bit for bit: an A/B switch for tests and timing)
+  const char *edge_env = getenv("FPL_VGG_EDGE_BLOCKS");
+  const int edge_blocks = edge_env ? atoi(edge_env) != 0 : 1;
   FPL_REQUIRE(ctx, (int64_t)S_TZ * SY * SX < ((int64_t)1 << 31),
               "vgg split path: a %lld x %lld plane is too large for the stem's 31-bit row "
               "offsets", (long long)SY, (long long)SX);
@@ -1774,6 +1864,7 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
       a.flag = flag; a.xlim = st->xlim; a.dump = (unsigned char *)dumpv;
       a.nbx = (int)ceil_div64(P1X, S_PX); a.nby = (int)ceil_div64(P1Y, S_PY);
       a.nbz = (int)ceil_div64(P1Z, S_PZ);
+      a.trim = edge_blocks;
       // persistent: one workgroup of 8 waves per CU walks the blocks
       const unsigned grid = (unsigned)std::min<int64_t>((int64_t)a.nbx * a.nby * a.nbz,
                                                         (int64_t)ctx->n_cu);
