@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <atomic>
 #include <map>
@@ -188,6 +189,33 @@ struct DevTemp {
       }
   }
 };
+
+// Scratch budget of the fused vgg executors (vgg_plan.h sizes their chunks by it):
+// FPL_VGG_SCRATCH_MB when set (tests shrink it to force several chunks), else the executor's
+// default.  The two defaults differ and nobody has measured why they should: 48 GiB for
+// vgg_like on plain 16-bit operands, 64 GiB for the other three executors.
+constexpr int64_t FPL_VGG_SCRATCH_PLAIN_VGG = (int64_t)48 << 30;
+constexpr int64_t FPL_VGG_SCRATCH_DEFAULT = (int64_t)64 << 30;
+static inline int64_t fpl_vgg_scratch_budget(int64_t dflt) {
+  const char *env = getenv("FPL_VGG_SCRATCH_MB");
+  return env ? (int64_t)atoll(env) << 20 : dflt;
+}
+
+// Replaces a fast-path state's device weight set (all fragments, all shift vectors) from the
+// two host vectors
+static inline int fpl_upload_weight_set(fpl_ctx *ctx, const std::vector<uint16_t> &frags,
+                                        const std::vector<float> &shifts, unsigned char **d_frags,
+                                        float **d_shifts) {
+  if (*d_frags) FPL_HIP(ctx, hipFree(*d_frags));
+  if (*d_shifts) FPL_HIP(ctx, hipFree(*d_shifts));
+  *d_frags = nullptr;
+  *d_shifts = nullptr;
+  FPL_HIP(ctx, hipMalloc((void **)d_frags, frags.size() * sizeof(uint16_t)));
+  FPL_HIP(ctx, hipMalloc((void **)d_shifts, shifts.size() * sizeof(float)));
+  FPL_HIP(ctx, hipMemcpy(*d_frags, frags.data(), frags.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  FPL_HIP(ctx, hipMemcpy(*d_shifts, shifts.data(), shifts.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
 
 // timing scope: records start/stop events around a launch when enabled
 struct TimedLaunch {

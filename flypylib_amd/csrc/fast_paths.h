@@ -32,6 +32,11 @@ static inline int fpl_vgg_variant(const fpl_program *prog) {
   if (prog->out_tensor != prog->ops[9].dst) return 0;
   return k2 == 1 ? 1 : 2;
 }
+// The eight convolutions L1..L8 of such a program (indices into prog->ops; 2 and 5 are the
+// pools) and the 16-row M-blocks of each one's output channels
+constexpr int FPL_VGG_CONV_OPS[8] = {0, 1, 3, 4, 6, 7, 8, 9};
+constexpr int FPL_VGG_MBLOCKS[8] = {3, 3, 3, 3, 3, 6, 6, 1};
+
 // one tile of the reference lattice (flypylib/fplnetwork.py:146-160)
 struct FplTileDesc {
   int32_t start[3];   // input window origin in the volume

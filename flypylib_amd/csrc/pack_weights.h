@@ -157,3 +157,60 @@ static inline void fpl_pack_stem(const float *W, const float *scale, int cout,
         }
       }
 }
+
+// ---- split weight sets (vgg_split.hip) -------------------------------------------
+// A 3x3x3 convolution W [27 * cin][cout] computed in `npass` passes of `chp` input channels:
+// per pass the (tap, channel-in-pass) sub-matrix as `ksteps` K-steps of 3 M-blocks, appended
+// to *out as [pass][K-step][part][b] - a pass's fragments are one contiguous run.
+static inline void fpl_pack_passes_split(const float *W, const float *scale, int cin, int cout,
+                                         int npass, int chp, int ksteps, int il,
+                                         std::vector<uint16_t> *out) {
+  for (int pass = 0; pass < npass; ++pass) {
+    std::vector<float> wp((size_t)27 * chp * cout);
+    for (int tap = 0; tap < 27; ++tap)
+      for (int ch = 0; ch < chp; ++ch)
+        memcpy(&wp[((size_t)tap * chp + ch) * cout],
+               W + ((size_t)tap * cin + pass * chp + ch) * cout, cout * sizeof(float));
+    std::vector<uint16_t> f[2];
+    for (int part = 0; part < 2; ++part)
+      fpl_pack_frags(wp.data(), scale, 27, chp, cout, 3, ksteps, SLOT_SPATIAL, &f[part], il, part);
+    for (int s = 0; s < ksteps; ++s)
+      for (int part = 0; part < 2; ++part)
+        out->insert(out->end(), f[part].begin() + (size_t)s * 3 * 512,
+                    f[part].begin() + (size_t)(s + 1) * 3 * 512);
+  }
+}
+
+// The vgg_like2 split stem W [27][cout] (vggs2_conv3<STEM>): per pass the `chp` (<= 32)
+// channels of that pass as two M-blocks (the other rows zero), one K-step of 27 taps, k-slot
+// (g, j) = tap 8g + j; appended to *out as [pass][part][blk].
+static inline void fpl_pack_stem2_split(const float *W, const float *scale, int cout, int npass,
+                                        int chp, std::vector<uint16_t> *out) {
+  for (int pass = 0; pass < npass; ++pass) {
+    std::vector<float> wp((size_t)27 * 32, 0.f), sp(32, 0.f);
+    for (int tap = 0; tap < 27; ++tap)
+      for (int ch = 0; ch < chp; ++ch)
+        wp[(size_t)tap * 32 + ch] = W[(size_t)tap * cout + pass * chp + ch];
+    for (int ch = 0; ch < chp; ++ch) sp[ch] = scale[pass * chp + ch];
+    for (int part = 0; part < 2; ++part) {
+      std::vector<uint16_t> f;
+      fpl_pack_frags(wp.data(), sp.data(), 27, 1, 32, 2, 1, SLOT_SPATIAL, &f, 0, part);
+      out->insert(out->end(), f.begin(), f.end());
+    }
+  }
+}
+
+// true when any IEEE half of the set is Inf or NaN (a folded weight outside the half range)
+static inline bool fpl_any_half_nonfinite(const std::vector<uint16_t> &h) {
+  for (uint16_t v : h)
+    if ((v & 0x7C00u) == 0x7C00u) return true;
+  return false;
+}
+
+// appends a layer's shift vector, zero-padded to a multiple of 4 floats; returns its offset
+static inline size_t fpl_append_shifts(std::vector<float> *shifts, const float *s, int n) {
+  const size_t off = shifts->size();
+  shifts->insert(shifts->end(), s, s + n);
+  while (shifts->size() % 4) shifts->push_back(0.f);
+  return off;
+}

@@ -13,17 +13,15 @@
 // output voxel) and P2 (1.5 B) are the only intermediates in HBM.  BN is folded:
 // scale into the bf16 weights, shift as the accumulators' initial value.
 //
-// Lattice equivalence with FplNetwork.infer (flypylib/fplnetwork.py:146-187):
-// with out = 88 = 4*22 every reference tile's input origin is a multiple of the
-// network stride 4, so the coarse grid is anchored at the volume origin:
-// pred[7+p] = O[p/4] with O[i] seeing input [4i, 4i+18), zero (normalised) past
-// the volume end - independent of the tiling.  The kernels compute O directly.
+// Which coarse rows a slab of the tile lattice owns, how they are cut into chunks and why
+// that equals FplNetwork.infer's tiling: vgg_plan.h.
 #include <algorithm>
 #include <cmath>
 
 #include "fast_paths.h"
 #include "mfma_util.h"
 #include "pack_weights.h"
+#include "vgg_plan.h"
 #include "vgg_tiles.h"
 
 namespace {
@@ -922,9 +920,6 @@ void vgg_state_free(fpl_ctx *ctx, void *p) {
   delete s;
 }
 
-bool is_vgg_like(const fpl_program *prog) { return fpl_vgg_variant(prog) == 1; }
-bool is_vgg_like2(const fpl_program *prog) { return fpl_vgg_variant(prog) == 2; }
-
 int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
   VggFastState *st = (VggFastState *)prog->fast_state_h16[FPL_H16_SLOT];
   if (!st) {
@@ -934,9 +929,8 @@ int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
   }
   *out = st;
   if (st->version == prog->arena_version) return 0;
-  const bool v2 = is_vgg_like2(prog);
-  static const int conv_ops[8] = {0, 1, 3, 4, 6, 7, 8, 9};
-  static const int mblocks[8] = {3, 3, 3, 3, 3, 6, 6, 1};
+  const bool v2 = fpl_vgg_variant(prog) == 2;
+  const int *conv_ops = FPL_VGG_CONV_OPS, *mblocks = FPL_VGG_MBLOCKS;
   static const int ksteps1[8] = {1, 2, KSTEPS, 2, KSTEPS, 2, 3, 3};
   static const FplSlotMap maps1[8] = {SLOT_STEM, SLOT_CHAIN, SLOT_SPATIAL, SLOT_CHAIN,
                                       SLOT_SPATIAL, SLOT_CHAIN, SLOT_CHAIN, SLOT_CHAIN};
@@ -953,9 +947,6 @@ int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
     const fpl_op &op = prog->ops[conv_ops[l]];
     std::vector<uint16_t> f;
     std::vector<float> scale(A + op.scale_off, A + op.scale_off + op.cout);
-    if (l == 7) {
-      // sigmoid head: scale is 1 (no BN); keep it explicit anyway
-    }
     if (l == 0 && !v2)
       fpl_pack_stem(A + op.w_off, scale.data(), op.cout, &f);
     else
@@ -963,9 +954,7 @@ int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
                      mblocks[l], ksteps[l], maps[l], &f);
     st->off_w[l] = all.size() * sizeof(uint16_t);
     all.insert(all.end(), f.begin(), f.end());
-    st->off_s[l] = shifts.size();
-    shifts.insert(shifts.end(), A + op.shift_off, A + op.shift_off + op.cout);
-    while (shifts.size() % 4) shifts.push_back(0.f);
+    st->off_s[l] = fpl_append_shifts(&shifts, A + op.shift_off, op.cout);
   }
   st->have_scaled = false;
 #ifdef FPL_F16
@@ -1012,29 +1001,16 @@ int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
       fpl_pack_frags(w2.data(), sc2.data(), 1, o2.cin, o2.cout, mblocks[1], ksteps[1], maps[1], &f);
       st->off_w2s = all.size() * sizeof(uint16_t);
       all.insert(all.end(), f.begin(), f.end());
-      st->off_s1s = shifts.size();
-      shifts.insert(shifts.end(), sh1.begin(), sh1.end());
-      while (shifts.size() % 4) shifts.push_back(0.f);
-      st->have_scaled = true;
-      for (uint16_t h : f) st->have_scaled = st->have_scaled && (h & 0x7C00u) != 0x7C00u;
+      st->off_s1s = fpl_append_shifts(&shifts, sh1.data(), o1.cout);
+      st->have_scaled = !fpl_any_half_nonfinite(f);
     }
   }
-  for (uint16_t h : all)
-    FPL_REQUIRE(ctx, (h & 0x7C00u) != 0x7C00u,
-                "a folded weight exceeds the IEEE-half range (65504); use precision "
-                "bf16 or f32 for this network");
+  FPL_REQUIRE(ctx, !fpl_any_half_nonfinite(all),
+              "a folded weight exceeds the IEEE-half range (65504); use precision "
+              "bf16 or f32 for this network");
 #endif
   st->bias8 = A[prog->ops[9].shift_off];
-  if (st->frags) FPL_HIP(ctx, hipFree(st->frags));
-  if (st->shifts) FPL_HIP(ctx, hipFree(st->shifts));
-  st->frags = nullptr;
-  st->shifts = nullptr;
-  FPL_HIP(ctx, hipMalloc((void **)&st->frags, all.size() * sizeof(uint16_t)));
-  FPL_HIP(ctx, hipMalloc((void **)&st->shifts, shifts.size() * sizeof(float)));
-  FPL_HIP(ctx, hipMemcpy(st->frags, all.data(), all.size() * sizeof(uint16_t),
-                         hipMemcpyHostToDevice));
-  FPL_HIP(ctx, hipMemcpy(st->shifts, shifts.data(), shifts.size() * sizeof(float),
-                         hipMemcpyHostToDevice));
+  FPL_TRY(fpl_upload_weight_set(ctx, all, shifts, &st->frags, &st->shifts));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)FPLK(vgg_mid_pool)<false>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, M_SMEM));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)FPLK(vgg_mid_pool)<true>,
@@ -1060,10 +1036,10 @@ int vgg_prepare(fpl_ctx *ctx, fpl_program *prog, VggFastState **out) {
 bool FPLK(fpl_fast_path_available)(const fpl_program *prog, int precision,
                              const int32_t offset[3], const int32_t out_sz[3]) {
   if (precision != FPL_THIS_PREC) return false;
-  const bool v1 = is_vgg_like(prog), v2 = !v1 && is_vgg_like2(prog);
-  if (!v1 && !v2) return false;
+  const int variant = fpl_vgg_variant(prog);           // 1: vgg_like (offset 7), 2: vgg_like2 (10)
+  if (variant == 0) return false;
   for (int a = 0; a < 3; ++a)
-    if (offset[a] != (v1 ? 7 : 10) || out_sz[a] % 4 != 0) return false;
+    if (offset[a] != (variant == 1 ? 7 : 10) || out_sz[a] % 4 != 0) return false;
   return true;
 }
 
@@ -1074,47 +1050,38 @@ namespace {
 //   L3 = conv3(H1)                    vgg2_conv3<>
 //   Q  = pool(conv3(L3))              vgg2_conv3<POOL>         (quarter resolution)
 //   prediction = head(conv3(Q))       vgg_c5_tail
-// With out = 80 = 4 * 20 every reference tile's input origin is a multiple of the stride,
-// so as for vgg_like the coarse grid is anchored at the volume origin: pred[10 + p] =
-// O[p / 4], O[i] seeing input [4i, 4i + 24), zero (normalised) past the volume end.
+// (the slab's coarse rows and their chunks: vgg_plan.h)
 int vgg2_infer(fpl_ctx *ctx, VggFastState *st, const void *src, int src_dtype, float mean, float sd,
                const int64_t dims[3], const std::vector<int32_t> origins[3],
                const int32_t out_sz[3], int32_t zb, int32_t ze, float *dst) {
   hipStream_t stream = ctx->stream;
   constexpr int OFF = 10;
   const int64_t SZ = dims[0], SY = dims[1], SX = dims[2];
-  const int64_t VZ = SZ - 2 * OFF, VY = SY - 2 * OFF, VX = SX - 2 * OFF;
-  if (VZ <= 0 || VY <= 0 || VX <= 0 || zb >= ze) return 0;
-  const int64_t fz_lo = (int64_t)origins[0][zb] - OFF;
-  const int64_t fz_hi = std::min<int64_t>((int64_t)origins[0][ze - 1] - OFF + out_sz[0], VZ);
-  const int64_t cz_lo = fz_lo / 4, cz_hi = ceil_div64(fz_hi, 4);
-  const int CY = (int)ceil_div64(VY, 4), CX = (int)ceil_div64(VX, 4);
-  const int QY = CY + 2, QX = CX + 2, T3Y = 2 * QY + 2, T3X = 2 * QX + 2, HY = T3Y + 2, HX = T3X + 2;
-  const int64_t h_row = (int64_t)HY * HX * VOX_BYTES, t_row = (int64_t)T3Y * T3X * VOX_BYTES;
-  const char *budget_env = getenv("FPL_VGG_SCRATCH_MB");
-  const int64_t budget = budget_env ? (int64_t)atoll(budget_env) << 20 : (int64_t)64 << 30;
-  // H1 has 2 (cz + 2) + 4 rows, L3 two fewer
-  int64_t cz_chunk = std::max<int64_t>(4, (budget / (h_row + t_row) - 8) / 2);
-  cz_chunk = std::min<int64_t>(cz_chunk, cz_hi - cz_lo);
-  cz_chunk = (cz_chunk + 3) / 4 * 4;
+  const VggSlab s = vgg_slab(dims, origins[0], out_sz[0], zb, ze, OFF);
+  if (s.empty) return 0;
+  const Vgg2Pyramid py(s.CY), px(s.CX);
+  const int64_t h_row = (int64_t)py.H * px.H * VOX_BYTES, t_row = (int64_t)py.T3 * px.T3 * VOX_BYTES;
+  const int64_t cz_chunk = vgg_chunk_rows(fpl_vgg_scratch_budget(FPL_VGG_SCRATCH_DEFAULT), h_row + t_row,
+                                          Vgg2Pyramid(0).H, s.cz_hi - s.cz_lo);
+  const Vgg2Pyramid pz_max(cz_chunk);
   DevTemp tmp(ctx);
   void *h1v, *l3v, *qv;
-  FPL_TRY(tmp.alloc((size_t)(2 * cz_chunk + 8) * h_row, &h1v));
-  FPL_TRY(tmp.alloc((size_t)(2 * cz_chunk + 6) * t_row, &l3v));
-  FPL_TRY(tmp.alloc((size_t)(cz_chunk + 2) * QY * QX * VOX_BYTES, &qv));
+  FPL_TRY(tmp.alloc((size_t)pz_max.H * h_row, &h1v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.T3 * t_row, &l3v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.Q * py.Q * px.Q * VOX_BYTES, &qv));
   const unsigned char *F = st->frags;
   const float *S = st->shifts;
-  for (int64_t c0 = cz_lo; c0 < cz_hi; c0 += cz_chunk) {
-    const int CZ = (int)std::min<int64_t>(cz_chunk, cz_hi - c0);
-    const int QZ = CZ + 2, T3Z = 2 * QZ + 2, HZ = T3Z + 2;
+  for (int64_t c0 = s.cz_lo; c0 < s.cz_hi; c0 += cz_chunk) {
+    const int CZ = (int)std::min<int64_t>(cz_chunk, s.cz_hi - c0);
+    const Vgg2Pyramid pz(CZ);
     {
       V2Args a = {};
       a.src = src; a.SZ = SZ; a.SY = SY; a.SX = SX; a.mean = mean; a.sd = sd;
       a.gz0 = 4 * c0;
       a.wstem = (const h16x8 *)(F + st->off_w[0]); a.shstem = S + st->off_s[0];
       a.w = F + st->off_w[1]; a.shift = S + st->off_s[1];
-      a.out = (h16_t *)h1v; a.OZ = HZ; a.OY = HY; a.OX = HX;
-      a.bg = BlockGrid{(int)ceil_div64(HX, 8), (int)ceil_div64(HY, 2), (int)ceil_div64(HZ, 2)};
+      a.out = (h16_t *)h1v; a.OZ = pz.H; a.OY = py.H; a.OX = px.H;
+      a.bg = BlockGrid{(int)ceil_div64(px.H, 8), (int)ceil_div64(py.H, 2), (int)ceil_div64(pz.H, 2)};
       TimedLaunch tl(ctx, "vgg2_stem_conv3_pool_" FPL_PREC_STR);
       if (src_dtype == FPL_U8)
         FPLK(vgg2_conv3)<true, true, uint8_t><<<block_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
@@ -1123,32 +1090,32 @@ int vgg2_infer(fpl_ctx *ctx, VggFastState *st, const void *src, int src_dtype, f
     }
     {
       V2Args a = {};
-      a.in = (const h16_t *)h1v; a.IZ = HZ; a.IY = HY; a.IX = HX;
+      a.in = (const h16_t *)h1v; a.IZ = pz.H; a.IY = py.H; a.IX = px.H;
       a.w = F + st->off_w[2]; a.shift = S + st->off_s[2];
-      a.out = (h16_t *)l3v; a.OZ = T3Z; a.OY = T3Y; a.OX = T3X;
-      a.bg = BlockGrid{(int)ceil_div64(T3X, 16), (int)ceil_div64(T3Y, 4), (int)ceil_div64(T3Z, 4)};
+      a.out = (h16_t *)l3v; a.OZ = pz.T3; a.OY = py.T3; a.OX = px.T3;
+      a.bg = BlockGrid{(int)ceil_div64(px.T3, 16), (int)ceil_div64(py.T3, 4), (int)ceil_div64(pz.T3, 4)};
       TimedLaunch tl(ctx, "vgg2_conv3_" FPL_PREC_STR);
       FPLK(vgg2_conv3)<false, false, uint8_t><<<block_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
     }
     {
       V2Args a = {};
-      a.in = (const h16_t *)l3v; a.IZ = T3Z; a.IY = T3Y; a.IX = T3X;
+      a.in = (const h16_t *)l3v; a.IZ = pz.T3; a.IY = py.T3; a.IX = px.T3;
       a.w = F + st->off_w[3]; a.shift = S + st->off_s[3];
-      a.out = (h16_t *)qv; a.OZ = QZ; a.OY = QY; a.OX = QX;
-      a.bg = BlockGrid{(int)ceil_div64(QX, 8), (int)ceil_div64(QY, 2), (int)ceil_div64(QZ, 2)};
+      a.out = (h16_t *)qv; a.OZ = pz.Q; a.OY = py.Q; a.OX = px.Q;
+      a.bg = BlockGrid{(int)ceil_div64(px.Q, 8), (int)ceil_div64(py.Q, 2), (int)ceil_div64(pz.Q, 2)};
       TimedLaunch tl(ctx, "vgg2_conv3_pool_" FPL_PREC_STR);
       FPLK(vgg2_conv3)<false, true, uint8_t><<<block_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
     }
     {
       C5TailArgs a;
-      a.p2 = (const h16_t *)qv; a.P2Z = QZ; a.P2Y = QY; a.P2X = QX;
+      a.p2 = (const h16_t *)qv; a.P2Z = pz.Q; a.P2Y = py.Q; a.P2X = px.Q;
       a.w5 = F + st->off_w[4]; a.shift5 = S + st->off_s[4];
-      a.CZ = CZ; a.CY = CY; a.CX = CX;
+      a.CZ = CZ; a.CY = s.CY; a.CX = s.CX;
       a.wtail = F + st->off_w[5];
       a.shift6 = S + st->off_s[5]; a.shift7 = S + st->off_s[6]; a.bias8 = st->bias8;
       a.dst = dst; a.DY = SY; a.DX = SX; a.gz0 = c0;
-      a.VZ = std::min<int64_t>(fz_hi, VZ); a.VY = VY; a.VX = VX; a.off = OFF;
-      a.bg = BlockGrid{(int)ceil_div64(CX, 16), (int)ceil_div64(CY, 4), (int)ceil_div64(CZ, 4)};
+      a.VZ = s.fz_hi; a.VY = s.VY; a.VX = s.VX; a.off = OFF;
+      a.bg = BlockGrid{(int)ceil_div64(s.CX, 16), (int)ceil_div64(s.CY, 4), (int)ceil_div64(CZ, 4)};
       TimedLaunch tl(ctx, "vgg_c5_tail_" FPL_PREC_STR);
       FPLK(vgg_c5_tail)<<<block_grid_size(a.bg), 256, H_SMEM, stream>>>(a);
     }
@@ -1170,41 +1137,36 @@ int FPLK(fpl_fast_infer_volume)(fpl_ctx *ctx, fpl_program *prog, const void *src
   if (!FPLK(fpl_fast_path_available)(prog, precision, offset, out_sz)) return 0;
   VggFastState *st;
   FPL_TRY(vgg_prepare(ctx, prog, &st));
-  if (is_vgg_like2(prog)) {
+  if (fpl_vgg_variant(prog) == 2) {
     FPL_TRY(vgg2_infer(ctx, st, src, src_dtype, mean, sd, dims, origins, out_sz, zb, ze, dst));
     *handled = true;
     return 0;
   }
   hipStream_t stream = ctx->stream;
   const int64_t SZ = dims[0], SY = dims[1], SX = dims[2];
-  const int64_t VZ = SZ - 14, VY = SY - 14, VX = SX - 14;
-  if (VZ <= 0 || VY <= 0 || VX <= 0 || zb >= ze) {   // no valid output voxel
+  const VggSlab s = vgg_slab(dims, origins[0], out_sz[0], zb, ze, 7);
+  if (s.empty) {   // no valid output voxel
     *handled = true;
     return 0;
   }
-  // coarse rows this slab owns (tile rows zb..ze-1 of the reference lattice)
-  const int64_t fz_lo = (int64_t)origins[0][zb] - 7;
-  const int64_t fz_hi = std::min<int64_t>((int64_t)origins[0][ze - 1] - 7 + out_sz[0], VZ);
-  const int64_t cz_lo = fz_lo / 4, cz_hi = ceil_div64(fz_hi, 4);
-  const int CY = (int)ceil_div64(VY, 4), CX = (int)ceil_div64(VX, 4);
-  const int P2Y = CY + 2, P2X = CX + 2, P1Y = 2 * P2Y + 2, P1X = 2 * P2X + 2;
+  const VggPyramid py(s.CY), px(s.CX);
   // chunk of coarse rows bounded by a scratch budget (P1 dominates)
-  const int64_t p1_row_bytes = (int64_t)P1Y * P1X * VOX_BYTES;
-  // (FPL_VGG_SCRATCH_MB shrinks it so that tests can force several chunks)
-  const char *budget_env = getenv("FPL_VGG_SCRATCH_MB");
-  const int64_t budget = budget_env ? (int64_t)atoll(budget_env) << 20 : (int64_t)48 << 30;
-  int64_t cz_chunk = std::max<int64_t>(4, (budget / p1_row_bytes - 6) / 2);
-  cz_chunk = std::min<int64_t>(cz_chunk, cz_hi - cz_lo);
-  cz_chunk = (cz_chunk + 3) / 4 * 4;
+  const int64_t p1_row_bytes = (int64_t)py.P1 * px.P1 * VOX_BYTES;
+  const int64_t cz_chunk = vgg_chunk_rows(fpl_vgg_scratch_budget(FPL_VGG_SCRATCH_PLAIN_VGG), p1_row_bytes,
+                                          VggPyramid(0).P1, s.cz_hi - s.cz_lo);
+  FPL_REQUIRE(ctx, (int64_t)S_TZ * SY * SX < ((int64_t)1 << 31),
+              "vgg fused path: a %lld x %lld plane is too large for the stem's 31-bit row "
+              "offsets", (long long)SY, (long long)SX);
+  const VggPyramid pz_max(cz_chunk);
   DevTemp tmp(ctx);
   void *p1v, *p2v;
-  FPL_TRY(tmp.alloc((size_t)(2 * cz_chunk + 6) * p1_row_bytes, &p1v));
-  FPL_TRY(tmp.alloc((size_t)(cz_chunk + 2) * P2Y * P2X * VOX_BYTES, &p2v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.P1 * p1_row_bytes, &p1v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.P2 * py.P2 * px.P2 * VOX_BYTES, &p2v));
   const unsigned char *F = st->frags;
   const float *S = st->shifts;
-  for (int64_t c0 = cz_lo; c0 < cz_hi; c0 += cz_chunk) {
-    const int CZ = (int)std::min<int64_t>(cz_chunk, cz_hi - c0);
-    const int P2Z = CZ + 2, P1Z = 2 * P2Z + 2;
+  for (int64_t c0 = s.cz_lo; c0 < s.cz_hi; c0 += cz_chunk) {
+    const int CZ = (int)std::min<int64_t>(cz_chunk, s.cz_hi - c0);
+    const VggPyramid pz(CZ);
     {
       StemArgs a;
       a.src = src; a.SZ = SZ; a.SY = SY; a.SX = SX; a.mean = mean; a.sd = sd;
@@ -1226,12 +1188,9 @@ int FPLK(fpl_fast_infer_volume)(fpl_ctx *ctx, fpl_program *prog, const void *src
         a.w2 = (const h16x8 *)(F + st->off_w2s);
         a.shift1 = S + st->off_s1s;
       }
-      a.p1 = (h16_t *)p1v; a.P1Z = P1Z; a.P1Y = P1Y; a.P1X = P1X;
-      a.nbx = (int)ceil_div64(P1X, S_PX); a.nby = (int)ceil_div64(P1Y, S_PY);
-      a.nbz = (int)ceil_div64(P1Z, S_PZ);
-      FPL_REQUIRE(ctx, (int64_t)S_TZ * SY * SX < ((int64_t)1 << 31),
-                  "vgg fused path: a %lld x %lld plane is too large for the stem's 31-bit row "
-                  "offsets", (long long)SY, (long long)SX);
+      a.p1 = (h16_t *)p1v; a.P1Z = pz.P1; a.P1Y = py.P1; a.P1X = px.P1;
+      a.nbx = (int)ceil_div64(px.P1, S_PX); a.nby = (int)ceil_div64(py.P1, S_PY);
+      a.nbz = (int)ceil_div64(pz.P1, S_PZ);
       // persistent: two workgroups per CU walk the blocks
       const unsigned grid = (unsigned)std::min<int64_t>((int64_t)a.nbx * a.nby * a.nbz,
                                                         (int64_t)ctx->n_cu * 2);
@@ -1245,12 +1204,12 @@ int FPLK(fpl_fast_infer_volume)(fpl_ctx *ctx, fpl_program *prog, const void *src
     }
     {
       MidArgs a;
-      a.p1 = (const h16_t *)p1v; a.P1Z = P1Z; a.P1Y = P1Y; a.P1X = P1X;
+      a.p1 = (const h16_t *)p1v; a.P1Z = pz.P1; a.P1Y = py.P1; a.P1X = px.P1;
       a.w3 = F + st->off_w[2];
       a.w4 = (const h16x8 *)(F + st->off_w[3]);
       a.shift3 = S + st->off_s[2]; a.shift4 = S + st->off_s[3];
-      a.p2 = (h16_t *)p2v; a.P2Z = P2Z; a.P2Y = P2Y; a.P2X = P2X;
-      a.bg = BlockGrid{(int)ceil_div64(P2X, 8), (int)ceil_div64(P2Y, 2), (int)ceil_div64(P2Z, 2)};
+      a.p2 = (h16_t *)p2v; a.P2Z = pz.P2; a.P2Y = py.P2; a.P2X = px.P2;
+      a.bg = BlockGrid{(int)ceil_div64(px.P2, 8), (int)ceil_div64(py.P2, 2), (int)ceil_div64(pz.P2, 2)};
       const unsigned grid = block_grid_size(a.bg);
       a.dbg = nullptr;
       if (getenv("FPL_DIAG_MID")) {
@@ -1283,14 +1242,14 @@ int FPLK(fpl_fast_infer_volume)(fpl_ctx *ctx, fpl_program *prog, const void *src
     }
     {
       C5TailArgs a;
-      a.p2 = (const h16_t *)p2v; a.P2Z = P2Z; a.P2Y = P2Y; a.P2X = P2X;
+      a.p2 = (const h16_t *)p2v; a.P2Z = pz.P2; a.P2Y = py.P2; a.P2X = px.P2;
       a.w5 = F + st->off_w[4]; a.shift5 = S + st->off_s[4];
-      a.CZ = CZ; a.CY = CY; a.CX = CX;
+      a.CZ = CZ; a.CY = s.CY; a.CX = s.CX;
       a.wtail = F + st->off_w[5];      // L6, L7, L8 fragments are contiguous
       a.shift6 = S + st->off_s[5]; a.shift7 = S + st->off_s[6]; a.bias8 = st->bias8;
       a.dst = dst; a.DY = SY; a.DX = SX; a.gz0 = c0;
-      a.VZ = std::min<int64_t>(fz_hi, VZ); a.VY = VY; a.VX = VX; a.off = 7;
-      a.bg = BlockGrid{(int)ceil_div64(CX, 16), (int)ceil_div64(CY, 4), (int)ceil_div64(CZ, 4)};
+      a.VZ = s.fz_hi; a.VY = s.VY; a.VX = s.VX; a.off = 7;
+      a.bg = BlockGrid{(int)ceil_div64(s.CX, 16), (int)ceil_div64(s.CY, 4), (int)ceil_div64(CZ, 4)};
       TimedLaunch tl(ctx, "vgg_c5_tail_" FPL_PREC_STR);
       FPLK(vgg_c5_tail)<<<block_grid_size(a.bg), 256, H_SMEM, stream>>>(a);
     }

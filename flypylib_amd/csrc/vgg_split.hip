@@ -29,6 +29,7 @@
 #include "fast_paths.h"
 #include "mfma_util.h"
 #include "pack_weights.h"
+#include "vgg_plan.h"
 #include <type_traits>
 #include "vgg_split_lds.h"
 #include "vgg_tiles.h"
@@ -1453,8 +1454,7 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
   }
   *out = st;
   if (st->version == prog->arena_version) return 0;
-  static const int conv_ops[8] = {0, 1, 3, 4, 6, 7, 8, 9};
-  static const int mblocks[8] = {3, 3, 3, 3, 3, 6, 6, 1};
+  const int *conv_ops = FPL_VGG_CONV_OPS, *mblocks = FPL_VGG_MBLOCKS;
   static const int ksteps[8] = {1, 2, KS, 2, KS, 2, 3, 3};
   const bool v2 = fpl_vgg_variant(prog) == 2;        // vgg_like2: L2 and L4 are 3x3x3 as well
   std::vector<uint16_t> all;
@@ -1465,20 +1465,7 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
     std::vector<float> scale(A + op.scale_off, A + op.scale_off + op.cout);
     st->off_w[l] = all.size() * sizeof(uint16_t);
     if (l == 0 && v2) {
-      // vggs2_conv3<STEM>: per pass the 24 channels of that pass as two M-blocks (8 zero
-      // rows), one K-step of 27 taps, k-slot (g, j) = tap 8g + j: [pass][part][blk]
-      for (int pass = 0; pass < NPASS; ++pass) {
-        std::vector<float> wp((size_t)27 * 32, 0.f), sp(32, 0.f);
-        for (int tap = 0; tap < 27; ++tap)
-          for (int ch = 0; ch < CHP; ++ch)
-            wp[(size_t)tap * 32 + ch] = A[op.w_off + (size_t)tap * op.cout + pass * CHP + ch];
-        for (int ch = 0; ch < CHP; ++ch) sp[ch] = scale[pass * CHP + ch];
-        for (int part = 0; part < 2; ++part) {
-          std::vector<uint16_t> f;
-          fpl_pack_frags(wp.data(), sp.data(), 27, 1, 32, 2, 1, SLOT_SPATIAL, &f, false, part);
-          all.insert(all.end(), f.begin(), f.end());
-        }
-      }
+      fpl_pack_stem2_split(A + op.w_off, scale.data(), op.cout, NPASS, CHP, &all);   // vggs2_conv3<STEM>
     } else if (l == 0) {
       for (int part = 0; part < 2; ++part) {       // [part][e][b]
         std::vector<uint16_t> f;
@@ -1488,39 +1475,10 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
     } else if (op.k == 3 && !v2) {
       // vgg_like (vgg_split_lds.h): passes of 8 channels, [pass 6][K-step 7][part][b] - a pass's
       // 42 fragments are one contiguous 42-KiB run for the LDS-DMA
-      for (int pass = 0; pass < x8::NQ; ++pass) {
-        std::vector<float> wp((size_t)27 * x8::CQ * op.cout);
-        for (int tap = 0; tap < 27; ++tap)
-          for (int ch = 0; ch < x8::CQ; ++ch)
-            memcpy(&wp[((size_t)tap * x8::CQ + ch) * op.cout],
-                   A + op.w_off + ((size_t)tap * op.cin + pass * x8::CQ + ch) * op.cout,
-                   op.cout * sizeof(float));
-        std::vector<uint16_t> f[2];
-        for (int part = 0; part < 2; ++part)
-          fpl_pack_frags(wp.data(), scale.data(), 27, x8::CQ, op.cout, 3, x8::KQ, SLOT_SPATIAL, &f[part], 0, part);
-        for (int s = 0; s < x8::KQ; ++s)
-          for (int part = 0; part < 2; ++part)
-            all.insert(all.end(), f[part].begin() + (size_t)s * 3 * 512,
-                       f[part].begin() + (size_t)(s + 1) * 3 * 512);
-      }
+      fpl_pack_passes_split(A + op.w_off, scale.data(), op.cin, op.cout, x8::NQ, x8::CQ, x8::KQ, 0, &all);
     } else if (op.k == 3) {
-      // [pass][K-step][part][b]: per pass the (tap, channel-in-pass) sub-matrix
-      for (int pass = 0; pass < NPASS; ++pass) {
-        std::vector<float> wp((size_t)27 * CHP * op.cout);
-        for (int tap = 0; tap < 27; ++tap)
-          for (int ch = 0; ch < CHP; ++ch)
-            memcpy(&wp[((size_t)tap * CHP + ch) * op.cout],
-                   A + op.w_off + ((size_t)tap * op.cin + pass * CHP + ch) * op.cout,
-                   op.cout * sizeof(float));
-        std::vector<uint16_t> f[2];
-        for (int part = 0; part < 2; ++part)
-          fpl_pack_frags(wp.data(), scale.data(), 27, CHP, op.cout, 3, KS, SLOT_SPATIAL, &f[part],
-                         /*il=*/v2 && l >= 1 && l <= 3, part);     // vggs2_conv3 stores 12-channel runs
-        for (int s = 0; s < KS; ++s)
-          for (int part = 0; part < 2; ++part)
-            all.insert(all.end(), f[part].begin() + (size_t)s * 3 * 512,
-                       f[part].begin() + (size_t)(s + 1) * 3 * 512);
-      }
+      fpl_pack_passes_split(A + op.w_off, scale.data(), op.cin, op.cout, NPASS, CHP, KS,
+                            /*il=*/v2 && l >= 1 && l <= 3, &all);     // vggs2_conv3 stores 12-channel runs
     } else if (op.cin == CH) {
       // chain48 steps: [blocks 0,1 hi], [blocks 0,1 lo], [blk 2: lo | hi], [blk 2: hi | lo]
       static const int blk[4][2] = {{0, 1}, {0, 1}, {2, 2}, {2, 2}};
@@ -1538,14 +1496,11 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
         all.insert(all.end(), f.begin(), f.end());
       }
     }
-    st->off_s[l] = shifts.size();
-    shifts.insert(shifts.end(), A + op.shift_off, A + op.shift_off + op.cout);
-    while (shifts.size() % 4) shifts.push_back(0.f);
+    st->off_s[l] = fpl_append_shifts(&shifts, A + op.shift_off, op.cout);
   }
-  for (uint16_t h : all)
-    if ((h & 0x7C00u) == 0x7C00u)
-      return fpl_fail_range(ctx, "a folded weight exceeds the IEEE-half range (65504); use precision "
-                                 "f32 (or 'auto') for this network");
+  if (fpl_any_half_nonfinite(all))
+    return fpl_fail_range(ctx, "a folded weight exceeds the IEEE-half range (65504); use precision "
+                               "f32 (or 'auto') for this network");
   {
     const fpl_op &op0 = prog->ops[0];
     std::vector<float> sh48(48, 0.f);
@@ -1556,16 +1511,7 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
                                  "(or 'auto') for this network");
   }
   st->bias8 = A[prog->ops[9].shift_off];
-  if (st->frags) FPL_HIP(ctx, hipFree(st->frags));
-  if (st->shifts) FPL_HIP(ctx, hipFree(st->shifts));
-  st->frags = nullptr;
-  st->shifts = nullptr;
-  FPL_HIP(ctx, hipMalloc((void **)&st->frags, all.size() * sizeof(uint16_t)));
-  FPL_HIP(ctx, hipMalloc((void **)&st->shifts, shifts.size() * sizeof(float)));
-  FPL_HIP(ctx, hipMemcpy(st->frags, all.data(), all.size() * sizeof(uint16_t),
-                         hipMemcpyHostToDevice));
-  FPL_HIP(ctx, hipMemcpy(st->shifts, shifts.data(), shifts.size() * sizeof(float),
-                         hipMemcpyHostToDevice));
+  FPL_TRY(fpl_upload_weight_set(ctx, all, shifts, &st->frags, &st->shifts));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_stem_pool<uint8_t>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_stem_pool<float>,
@@ -1616,19 +1562,8 @@ int split_prepare_int(fpl_ctx *ctx, fpl_program *prog, SplitState *st, float mea
   }
   st->w1_int_host.clear();
   if (fpl_vgg_variant(prog) == 2) {
-    // vggs2_conv3<STEM>: [pass][part][blk] as in split_prepare, with 1 / sd in the scale
-    for (int pass = 0; pass < NPASS; ++pass) {
-      std::vector<float> wp((size_t)27 * 32, 0.f), sp(32, 0.f);
-      for (int tap = 0; tap < 27; ++tap)
-        for (int ch = 0; ch < CHP; ++ch)
-          wp[(size_t)tap * 32 + ch] = A[op.w_off + (size_t)tap * op.cout + pass * CHP + ch];
-      for (int ch = 0; ch < CHP; ++ch) sp[ch] = scale[pass * CHP + ch];
-      for (int part = 0; part < 2; ++part) {
-        std::vector<uint16_t> f;
-        fpl_pack_frags(wp.data(), sp.data(), 27, 1, 32, 2, 1, SLOT_SPATIAL, &f, false, part);
-        st->w1_int_host.insert(st->w1_int_host.end(), f.begin(), f.end());
-      }
-    }
+    // vggs2_conv3<STEM>: as in split_prepare, with 1 / sd in the scale
+    fpl_pack_stem2_split(A + op.w_off, scale.data(), op.cout, NPASS, CHP, &st->w1_int_host);
     st->w1_int_host.resize((size_t)2 * 6 * 512, 0);          // the buffer's fixed size
   } else {
     for (int part = 0; part < 2; ++part) {         // [part][e][b]
@@ -1637,10 +1572,9 @@ int split_prepare_int(fpl_ctx *ctx, fpl_program *prog, SplitState *st, float mea
       st->w1_int_host.insert(st->w1_int_host.end(), f.begin(), f.end());
     }
   }
-  for (uint16_t h : st->w1_int_host)
-    if ((h & 0x7C00u) == 0x7C00u)
-      return fpl_fail_range_call(ctx, "a first-layer weight divided by std %g exceeds the IEEE-half range; use "
-                                 "precision f32 (or 'auto') for this normalisation", (double)sd);
+  if (fpl_any_half_nonfinite(st->w1_int_host))
+    return fpl_fail_range_call(ctx, "a first-layer weight divided by std %g exceeds the IEEE-half range; use "
+                               "precision f32 (or 'auto') for this normalisation", (double)sd);
   // half-range guard: the operand is |u - c0| <= max(c0, 255 - c0)
   if (!(stem_input_limit(A, op, scale.data(), st->shift1_int_host.data(), 64) >= std::max(c0, 255.0 - c0)))
     return fpl_fail_range_call(ctx, "the first layer's outputs may exceed the IEEE-half range at mean %g, std %g; "
@@ -1671,8 +1605,8 @@ bool fpl_split_path_available(const fpl_program *prog, int precision, const int3
 
 namespace {
 
-// vgg_like2 over the coarse rows of a slab, as vgg_fused.hip::vgg2_infer (where the lattice
-// argument is made): four launches per chunk, the three intermediate tensors in pass planes
+// vgg_like2 over the coarse rows of a slab (vgg_plan.h), as vgg_fused.hip::vgg2_infer: four
+// launches per chunk, the three intermediate tensors in pass planes
 //   H1 = pool(conv3(conv3(volume)))   vggs2_conv3<STEM, POOL>   (half resolution)
 //   L3 = conv3(H1)                    vggs2_conv3<>
 //   Q  = pool(conv3(L3))              vggs2_conv3<POOL>         (quarter resolution)
@@ -1683,35 +1617,28 @@ int split2_infer(fpl_ctx *ctx, SplitState *st, const void *src, int src_dtype, f
   hipStream_t stream = ctx->stream;
   constexpr int OFF = 10;
   const int64_t SZ = dims[0], SY = dims[1], SX = dims[2];
-  const int64_t VZ = SZ - 2 * OFF, VY = SY - 2 * OFF, VX = SX - 2 * OFF;
-  if (VZ <= 0 || VY <= 0 || VX <= 0 || zb >= ze) return 0;
-  const int64_t fz_lo = (int64_t)origins[0][zb] - OFF;
-  const int64_t fz_hi = std::min<int64_t>((int64_t)origins[0][ze - 1] - OFF + out_sz[0], VZ);
-  const int64_t cz_lo = fz_lo / 4, cz_hi = ceil_div64(fz_hi, 4);
-  const int CY = (int)ceil_div64(VY, 4), CX = (int)ceil_div64(VX, 4);
-  const int QY = CY + 2, QX = CX + 2, T3Y = 2 * QY + 2, T3X = 2 * QX + 2, HY = T3Y + 2, HX = T3X + 2;
-  const int64_t h_row = (int64_t)HY * HX * VOX, t_row = (int64_t)T3Y * T3X * VOX;
-  const char *budget_env = getenv("FPL_VGG_SCRATCH_MB");
-  const int64_t budget = budget_env ? (int64_t)atoll(budget_env) << 20 : (int64_t)64 << 30;
-  // H1 has 2 (cz + 2) + 4 rows, L3 two fewer
-  int64_t cz_chunk = std::max<int64_t>(4, (budget / (h_row + t_row) - 8) / 2);
-  cz_chunk = std::min<int64_t>(cz_chunk, cz_hi - cz_lo);
-  cz_chunk = (cz_chunk + 3) / 4 * 4;
-  FPL_REQUIRE(ctx, (int64_t)HY * HX * PASS_BYTES * 8 < ((int64_t)1 << 32),
+  const VggSlab s = vgg_slab(dims, origins[0], out_sz[0], zb, ze, OFF);
+  if (s.empty) return 0;
+  const Vgg2Pyramid py(s.CY), px(s.CX);
+  const int64_t h_row = (int64_t)py.H * px.H * VOX, t_row = (int64_t)py.T3 * px.T3 * VOX;
+  const int64_t cz_chunk = vgg_chunk_rows(fpl_vgg_scratch_budget(FPL_VGG_SCRATCH_DEFAULT), h_row + t_row,
+                                          Vgg2Pyramid(0).H, s.cz_hi - s.cz_lo);
+  const Vgg2Pyramid pz_max(cz_chunk);
+  FPL_REQUIRE(ctx, (int64_t)py.H * px.H * PASS_BYTES * 8 < ((int64_t)1 << 32),
               "vgg_like2 split path: a %lld x %lld plane is too large for the tile loader's 32-bit "
               "offsets", (long long)SY, (long long)SX);
   DevTemp tmp(ctx);
   unsigned *flag;
   FPL_TRY(fpl_range_flag(ctx, &flag));
   void *h1v, *l3v, *qv;
-  FPL_TRY(tmp.alloc((size_t)(2 * cz_chunk + 8) * h_row, &h1v));
-  FPL_TRY(tmp.alloc((size_t)(2 * cz_chunk + 6) * t_row, &l3v));
-  FPL_TRY(tmp.alloc((size_t)(cz_chunk + 2) * QY * QX * VOX, &qv));
+  FPL_TRY(tmp.alloc((size_t)pz_max.H * h_row, &h1v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.T3 * t_row, &l3v));
+  FPL_TRY(tmp.alloc((size_t)pz_max.Q * py.Q * px.Q * VOX, &qv));
   const unsigned char *F = st->frags;
   const float *S = st->shifts;
-  for (int64_t c0 = cz_lo; c0 < cz_hi; c0 += cz_chunk) {
-    const int CZ = (int)std::min<int64_t>(cz_chunk, cz_hi - c0);
-    const int QZ = CZ + 2, T3Z = 2 * QZ + 2, HZ = T3Z + 2;
+  for (int64_t c0 = s.cz_lo; c0 < s.cz_hi; c0 += cz_chunk) {
+    const int CZ = (int)std::min<int64_t>(cz_chunk, s.cz_hi - c0);
+    const Vgg2Pyramid pz(CZ);
     {
       V2SArgs a = {};
       a.src = src; a.SZ = SZ; a.SY = SY; a.SX = SX; a.mean = mean; a.sd = sd;
@@ -1721,9 +1648,9 @@ int split2_infer(fpl_ctx *ctx, SplitState *st, const void *src, int src_dtype, f
         a.wstem = (const h16x8 *)st->w1_int; a.shtab = st->shift1_int; a.c0 = st->int_c0;
       }
       a.w = F + st->off_w[1]; a.shift = S + st->off_s[1];
-      a.out = (unsigned char *)h1v; a.OZ = HZ; a.OY = HY; a.OX = HX;
+      a.out = (unsigned char *)h1v; a.OZ = pz.H; a.OY = py.H; a.OX = px.H;
       a.flag = flag; a.xlim = st->xlim;
-      a.bg = BlockGrid{(int)ceil_div64(HX, 8), (int)ceil_div64(HY, 2), (int)ceil_div64(HZ, 2)};
+      a.bg = BlockGrid{(int)ceil_div64(px.H, 8), (int)ceil_div64(py.H, 2), (int)ceil_div64(pz.H, 2)};
       TimedLaunch tl(ctx, "vggs2_stem_conv3_pool");
       if (src_dtype == FPL_U8)
         vggs2_conv3<true, true, uint8_t><<<brick_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
@@ -1732,35 +1659,35 @@ int split2_infer(fpl_ctx *ctx, SplitState *st, const void *src, int src_dtype, f
     }
     {
       V2SArgs a = {};
-      a.in = (const unsigned char *)h1v; a.IZ = HZ; a.IY = HY; a.IX = HX;
+      a.in = (const unsigned char *)h1v; a.IZ = pz.H; a.IY = py.H; a.IX = px.H;
       a.w = F + st->off_w[2]; a.shift = S + st->off_s[2];
-      a.out = (unsigned char *)l3v; a.OZ = T3Z; a.OY = T3Y; a.OX = T3X;
+      a.out = (unsigned char *)l3v; a.OZ = pz.T3; a.OY = py.T3; a.OX = px.T3;
       a.flag = flag;
-      a.bg = BlockGrid{(int)ceil_div64(T3X, 16), (int)ceil_div64(T3Y, 4), (int)ceil_div64(T3Z, 4)};
+      a.bg = BlockGrid{(int)ceil_div64(px.T3, 16), (int)ceil_div64(py.T3, 4), (int)ceil_div64(pz.T3, 4)};
       TimedLaunch tl(ctx, "vggs2_conv3");
       vggs2_conv3<false, false, uint8_t><<<brick_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
     }
     {
       V2SArgs a = {};
-      a.in = (const unsigned char *)l3v; a.IZ = T3Z; a.IY = T3Y; a.IX = T3X;
+      a.in = (const unsigned char *)l3v; a.IZ = pz.T3; a.IY = py.T3; a.IX = px.T3;
       a.w = F + st->off_w[3]; a.shift = S + st->off_s[3];
-      a.out = (unsigned char *)qv; a.OZ = QZ; a.OY = QY; a.OX = QX;
+      a.out = (unsigned char *)qv; a.OZ = pz.Q; a.OY = py.Q; a.OX = px.Q;
       a.flag = flag;
-      a.bg = BlockGrid{(int)ceil_div64(QX, 8), (int)ceil_div64(QY, 2), (int)ceil_div64(QZ, 2)};
+      a.bg = BlockGrid{(int)ceil_div64(px.Q, 8), (int)ceil_div64(py.Q, 2), (int)ceil_div64(pz.Q, 2)};
       TimedLaunch tl(ctx, "vggs2_conv3_pool");
       vggs2_conv3<false, true, uint8_t><<<brick_grid_size(a.bg), 256, V2_SMEM, stream>>>(a);
     }
     {
       TailSArgs a;
-      a.p2 = (const unsigned char *)qv; a.P2Z = QZ; a.P2Y = QY; a.P2X = QX;
+      a.p2 = (const unsigned char *)qv; a.P2Z = pz.Q; a.P2Y = py.Q; a.P2X = px.Q;
       a.w5 = F + st->off_w[4]; a.shift5 = S + st->off_s[4];
-      a.CZ = CZ; a.CY = CY; a.CX = CX;
+      a.CZ = CZ; a.CY = s.CY; a.CX = s.CX;
       a.w6 = F + st->off_w[5]; a.w7 = F + st->off_w[6]; a.w8 = F + st->off_w[7];
       a.shift6 = S + st->off_s[5]; a.shift7 = S + st->off_s[6]; a.bias8 = st->bias8;
       a.dst = dst; a.DY = SY; a.DX = SX; a.gz0 = c0;
-      a.VZ = std::min<int64_t>(fz_hi, VZ); a.VY = VY; a.VX = VX; a.off = OFF;
+      a.VZ = s.fz_hi; a.VY = s.VY; a.VX = s.VX; a.off = OFF;
       a.flag = flag;
-      a.bg = BlockGrid{(int)ceil_div64(CX, 16), (int)ceil_div64(CY, 4), (int)ceil_div64(CZ, 4)};
+      a.bg = BlockGrid{(int)ceil_div64(s.CX, 16), (int)ceil_div64(s.CY, 4), (int)ceil_div64(CZ, 4)};
       TimedLaunch tl(ctx, "vggs_c5_tail");
       vggs_c5_tail_p24<<<brick_grid_size(a.bg), 256, M_SMEM, stream>>>(a);
     }
@@ -1771,14 +1698,8 @@ int split2_infer(fpl_ctx *ctx, SplitState *st, const void *src, int src_dtype, f
 
 }  // namespace
 
-// Slab orchestration: as the vgg_like branch of fpl_fast_infer_volume_* (vgg_fused.hip;
-// the lattice equivalence with FplNetwork.infer, flypylib/fplnetwork.py:146-187, is
-// argued there), with P1 / P2 in the split layout.
-// Row pitch (voxels of 16 B) of an x8 tensor of X voxels per row.  (Pitches padded by 14 - 126
-// voxels were measured on the 520^3 volume - 4128-B rows - and changed nothing: what made that
-// size slow was the walk order, vgg_split_lds.h::Cursor.)
-static int x8_pitch(int X) { return X; }
-
+// Slab orchestration (the slab's coarse rows, their chunks and the lattice equivalence with
+// FplNetwork.infer: vgg_plan.h), with P1 / P2 in the split layout.
 int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int src_dtype,
                            float mean, float sd, const int64_t dims[3],
                            const std::vector<int32_t> origins[3], const int32_t out_sz[3],
@@ -1790,23 +1711,9 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
     return split2_infer(ctx, st, src, src_dtype, mean, sd, dims, origins, out_sz, zb, ze, dst);
   hipStream_t stream = ctx->stream;
   const int64_t SZ = dims[0], SY = dims[1], SX = dims[2];
-  const int64_t VZ = SZ - 14, VY = SY - 14, VX = SX - 14;
-  if (VZ <= 0 || VY <= 0 || VX <= 0 || zb >= ze) return 0;   // no valid output voxel
-  // coarse rows this slab owns (tile rows zb..ze-1 of the reference lattice)
-  const int64_t fz_lo = (int64_t)origins[0][zb] - 7;
-  const int64_t fz_hi = std::min<int64_t>((int64_t)origins[0][ze - 1] - 7 + out_sz[0], VZ);
-  const int64_t cz_lo = fz_lo / 4, cz_hi = ceil_div64(fz_hi, 4);
-  const int CY = (int)ceil_div64(VY, 4), CX = (int)ceil_div64(VX, 4);
-  const int P2Y = CY + 2, P2X = CX + 2, P1Y = 2 * P2Y + 2, P1X = 2 * P2X + 2;
-  const int P1XP = x8_pitch(P1X), P2XP = x8_pitch(P2X);       // row pitches (voxels)
-  // chunk of coarse rows bounded by a scratch budget (P1 dominates;
-  // FPL_VGG_SCRATCH_MB shrinks it so that tests can force several chunks)
-  const int64_t p1_row_bytes = (int64_t)P1Y * P1XP * VOX;
-  const char *budget_env = getenv("FPL_VGG_SCRATCH_MB");
-  const int64_t budget = budget_env ? (int64_t)atoll(budget_env) << 20 : (int64_t)64 << 30;
-  int64_t cz_chunk = std::max<int64_t>(4, (budget / p1_row_bytes - 6) / 2);
-  cz_chunk = std::min<int64_t>(cz_chunk, cz_hi - cz_lo);
-  cz_chunk = (cz_chunk + 3) / 4 * 4;
+  const VggSlab s = vgg_slab(dims, origins[0], out_sz[0], zb, ze, 7);
+  if (s.empty) return 0;   // no valid output voxel
+  const VggPyramid py(s.CY), px(s.CX);
   // FPL_VGG_EDGE_BLOCKS=0: the stem walks its partial blocks in full, as every block (same
   // results, bit for bit: an A/B switch for tests and timing)
   const char *edge_env = getenv("FPL_VGG_EDGE_BLOCKS");
@@ -1814,20 +1721,21 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
   FPL_REQUIRE(ctx, (int64_t)S_TZ * SY * SX < ((int64_t)1 << 31),
               "vgg split path: a %lld x %lld plane is too large for the stem's 31-bit row "
               "offsets", (long long)SY, (long long)SX);
-  // the tile loads address a pass's hi AND lo plane from one scalar base with 32-bit lane
-  // offsets: two part planes of the chunk plus the tile's reach stay below 4 GiB
-  {
-    const int64_t max_rows = (((int64_t)1 << 32) / 16 / ((int64_t)P1Y * P1XP) - (x8::TZ + 2));
-    FPL_REQUIRE(ctx, max_rows >= 14,
-                "vgg split path: a %lld x %lld plane is too large for the tile loader's 32-bit "
-                "offsets", (long long)SY, (long long)SX);
-    cz_chunk = std::min<int64_t>(cz_chunk, std::max<int64_t>(4, ((max_rows - 6) / 2) / 4 * 4));
-  }
+  // the tile loader's 32-bit offsets bound the P1 rows of a chunk (vgg_plan.h)
+  const int64_t max_rows = vgg_split_max_p1_rows(py.P1, px.P1, x8::TZ);
+  FPL_REQUIRE(ctx, max_rows >= 14,
+              "vgg split path: a %lld x %lld plane is too large for the tile loader's 32-bit "
+              "offsets", (long long)SY, (long long)SX);
+  // chunk of coarse rows bounded by a scratch budget (P1 dominates) and by that cap
+  const int64_t cz_chunk = vgg_chunk_rows(fpl_vgg_scratch_budget(FPL_VGG_SCRATCH_DEFAULT),
+                                          (int64_t)py.P1 * px.P1 * VOX, VggPyramid(0).P1, s.cz_hi - s.cz_lo,
+                                          vgg_split_chunk_cap(max_rows));
+  const VggPyramid pz_max(cz_chunk);
   DevTemp tmp(ctx);
   unsigned *flag;
   FPL_TRY(fpl_range_flag(ctx, &flag));
   // P1 / P2 as planes of 8-channel passes (vgg_split_lds.h) with read slack behind them
-  x8::Tensor p1 = {nullptr, (int)(2 * cz_chunk + 6), P1Y, P1X, P1XP}, p2 = {nullptr, (int)(cz_chunk + 2), P2Y, P2X, P2XP};
+  x8::Tensor p1 = {nullptr, pz_max.P1, py.P1, px.P1, px.P1}, p2 = {nullptr, pz_max.P2, py.P2, px.P2, px.P2};
   void *p1v, *p2v;
   FPL_TRY(tmp.alloc((size_t)(p1.bytes() + p1.slack_bytes()), &p1v));
   FPL_TRY(tmp.alloc((size_t)(p2.bytes() + p2.slack_bytes()), &p2v));
@@ -1837,11 +1745,11 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
   const unsigned pgrid = (unsigned)std::max(8, ctx->n_cu / 8 * 8);
   const unsigned char *F = st->frags;
   const float *S = st->shifts;
-  for (int64_t c0 = cz_lo; c0 < cz_hi; c0 += cz_chunk) {
-    const int CZ = (int)std::min<int64_t>(cz_chunk, cz_hi - c0);
-    const int P2Z = CZ + 2, P1Z = 2 * P2Z + 2;
-    p1 = x8::Tensor{(unsigned char *)p1v, P1Z, P1Y, P1X, P1XP};
-    p2 = x8::Tensor{(unsigned char *)p2v, P2Z, P2Y, P2X, P2XP};
+  for (int64_t c0 = s.cz_lo; c0 < s.cz_hi; c0 += cz_chunk) {
+    const int CZ = (int)std::min<int64_t>(cz_chunk, s.cz_hi - c0);
+    const VggPyramid pz(CZ);
+    p1 = x8::Tensor{(unsigned char *)p1v, pz.P1, py.P1, px.P1, px.P1};
+    p2 = x8::Tensor{(unsigned char *)p2v, pz.P2, py.P2, px.P2, px.P2};
     // edge tiles read up to TZ planes past the last pass plane: zeros, not stale scratch
     FPL_HIP(ctx, hipMemsetAsync(p1.p + p1.bytes(), 0, (size_t)p1.slack_bytes(), stream));
     FPL_HIP(ctx, hipMemsetAsync(p2.p + p2.bytes(), 0, (size_t)p2.slack_bytes(), stream));
@@ -1862,8 +1770,8 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
       }
       a.p1 = p1;
       a.flag = flag; a.xlim = st->xlim; a.dump = (unsigned char *)dumpv;
-      a.nbx = (int)ceil_div64(P1X, S_PX); a.nby = (int)ceil_div64(P1Y, S_PY);
-      a.nbz = (int)ceil_div64(P1Z, S_PZ);
+      a.nbx = (int)ceil_div64(px.P1, S_PX); a.nby = (int)ceil_div64(py.P1, S_PY);
+      a.nbz = (int)ceil_div64(pz.P1, S_PZ);
       a.trim = edge_blocks;
       // persistent: one workgroup of 8 waves per CU walks the blocks
       const unsigned grid = (unsigned)std::min<int64_t>((int64_t)a.nbx * a.nby * a.nbz,
@@ -1882,7 +1790,7 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
       a.shift3 = S + st->off_s[2]; a.shift4 = S + st->off_s[3];
       a.p2 = p2;
       a.flag = flag;
-      a.walk = x8::Walk{(int)ceil_div64(P2X, 8), (int)ceil_div64(P2Y, 2), (int)ceil_div64(P2Z, 4)};
+      a.walk = x8::Walk{(int)ceil_div64(px.P2, 8), (int)ceil_div64(py.P2, 2), (int)ceil_div64(pz.P2, 4)};
       TimedLaunch tl(ctx, "vggs_mid_pool");
       vggs_mid_pool<<<pgrid, 64 * x8::WAVES, x8::SMEM, stream>>>(a);
     }
@@ -1890,13 +1798,13 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
       TailXArgs a;
       a.p2 = p2;
       a.w5 = F + st->off_w[4]; a.shift5 = S + st->off_s[4];
-      a.CZ = CZ; a.CY = CY; a.CX = CX;
+      a.CZ = CZ; a.CY = s.CY; a.CX = s.CX;
       a.w6 = F + st->off_w[5]; a.w7 = F + st->off_w[6]; a.w8 = F + st->off_w[7];
       a.shift6 = S + st->off_s[5]; a.shift7 = S + st->off_s[6]; a.bias8 = st->bias8;
       a.dst = dst; a.DY = SY; a.DX = SX; a.gz0 = c0;
-      a.VZ = std::min<int64_t>(fz_hi, VZ); a.VY = VY; a.VX = VX; a.off = 7;
+      a.VZ = s.fz_hi; a.VY = s.VY; a.VX = s.VX; a.off = 7;
       a.flag = flag;
-      a.walk = x8::Walk{(int)ceil_div64(CX, 16), (int)ceil_div64(CY, 4), (int)ceil_div64(CZ, 8)};
+      a.walk = x8::Walk{(int)ceil_div64(s.CX, 16), (int)ceil_div64(s.CY, 4), (int)ceil_div64(CZ, 8)};
       TimedLaunch tl(ctx, "vggs_c5_tail");
       vggs_c5_tail<<<pgrid, 64 * x8::WAVES, x8::SMEM, stream>>>(a);
     }
