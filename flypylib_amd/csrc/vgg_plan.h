@@ -72,3 +72,80 @@ static inline int64_t vgg_split_max_p1_rows(int P1Y, int P1X, int tile_z) {
 static inline int64_t vgg_split_chunk_cap(int64_t max_rows) {
   return std::max<int64_t>(4, ((max_rows - VggPyramid(0).P1) / 2) / 4 * 4);
 }
+
+// ---- Split vgg_like, the mid kernel (conv3 + conv1 + pool: P1 -> P2): block orientations ----
+// A block is 8 waves x 4 sub-steps x 16 lanes = 512 pre-pool outputs (64 pooled voxels) on a tile
+// of P1 in LDS.  The interior orientation lays that out as 8 z x 4 y x 16 x.  Where P2 cuts the
+// last block column (x) or layer (z), most of such a block's lanes or waves hold no P2 voxel, and
+// the cut region is walked in an orientation whose SHORT axis is the cut one instead:
+//   MID_XCOL    8 z x 16 y x 4 x   lanes along y, sub-steps the (dz, dx) window, lane pair pools y
+//   MID_ZLAYER  4 z x 8 y x 16 x   waves along (z 2, y 4), sub-steps and lanes as in the interior
+// Only WHICH wave, sub-step and lane computes a voxel changes: the taps keep their numbering
+// (tap = (dz * 3 + dy) * 3 + dx) and with it every voxel its sequence of MFMAs.
+// (Plain constexpr functions: the kernels and the host compiler's tests share them.)
+enum { MID_INTERIOR = 0, MID_XCOL = 1, MID_ZLAYER = 2 };
+
+struct MidGeo {
+  int BZ, BY, BX;          // pre-pool outputs of a block; its tile is (BZ + 2) x (BY + 2) x (BX + 2)
+  int ZS;                  // LDS slots between z planes of the tile (rows are BX + 2 slots apart)
+  constexpr int TZ() const { return BZ + 2; }
+  constexpr int TY() const { return BY + 2; }
+  constexpr int TX() const { return BX + 2; }
+  constexpr int slots() const { return (TZ() - 1) * ZS + TY() * TX(); }
+  constexpr int slot(int tz, int ty, int tx) const { return tz * ZS + ty * TX() + tx; }
+};
+// (z strides: the interior's 118 is padded for conflict-free taps, vgg_split_lds.h; 182 likewise -
+// 182 - 2 * 18 - 2 = 144 = 0 mod 16; the x column's lanes are a row of 6 slots apart whatever the
+// padding, and 7 does not fit the tile's 1170 slots)
+constexpr MidGeo mid_geo(int o) {
+  return o == MID_XCOL ? MidGeo{8, 16, 4, 108} : o == MID_ZLAYER ? MidGeo{4, 8, 16, 182} : MidGeo{8, 4, 16, 118};
+}
+
+struct MidVox { int z, y, x; };
+// the pre-pool output, relative to its block, of wave `wave`, sub-step `sub`, lane column `c`
+// (= lane & 15).  Sub-step 0 of an even c is the even corner of a pooled voxel; its 2 x 2 x 2 window
+// is the four sub-steps of lanes c and c + 1.
+constexpr MidVox mid_voxel(int o, int wave, int sub, int c) {
+  return o == MID_XCOL     ? MidVox{2 * (wave >> 1) + (sub >> 1), c, 2 * (wave & 1) + (sub & 1)}
+         : o == MID_ZLAYER ? MidVox{2 * (wave >> 2) + (sub >> 1), 2 * (wave & 3) + (sub & 1), c}
+                           : MidVox{2 * (wave >> 1) + (sub >> 1), 2 * (wave & 1) + (sub & 1), c};
+}
+// the tile voxel that LDS slot `s` of a part plane holds; the padding between z planes and the slots
+// behind the tile repeat a voxel of the tile (loaded, never read)
+constexpr MidVox mid_slot_voxel(const MidGeo &g, int s) {
+  const int tz = s / g.ZS < g.TZ() ? s / g.ZS : g.TZ() - 1;
+  const int rem = s - tz * g.ZS < g.TY() * g.TX() ? s - tz * g.ZS : g.TY() * g.TX() - 1;
+  return MidVox{tz, rem / g.TX(), rem % g.TX()};
+}
+// slot offset of tap 0 .. 26 from an output voxel's own slot
+constexpr int mid_tap_slot(const MidGeo &g, int tap) { return g.slot(tap / 9, (tap / 3) % 3, tap % 3); }
+
+// The launches of the mid kernel over a P2 of (Z, Y, X) pooled voxels: per orientation a grid of
+// nbx x nby x nbz blocks whose first block starts at pre-pool (z0, 0, x0).  The interior launch
+// gives up its cut column / layer when the other orientation covers it in FEWER blocks (the
+// corner goes with the x column); an orientation with no block is not launched.
+struct MidWalk {
+  int nbx, nby, nbz;
+  int z0, x0;
+  constexpr int64_t blocks() const { return (int64_t)nbx * nby * nbz; }
+};
+struct MidPlan { MidWalk w[3]; };
+
+static inline MidPlan vgg_mid_plan(int Z, int Y, int X, bool reorient) {
+  auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
+  const MidGeo gi = mid_geo(MID_INTERIOR), gx = mid_geo(MID_XCOL), gz = mid_geo(MID_ZLAYER);
+  MidPlan p = {};
+  MidWalk &in = p.w[MID_INTERIOR], &xc = p.w[MID_XCOL], &zl = p.w[MID_ZLAYER];
+  in = MidWalk{cdiv(2 * X, gi.BX), cdiv(2 * Y, gi.BY), cdiv(2 * Z, gi.BZ), 0, 0};
+  if (!reorient) return p;
+  const int live_x = 2 * X % gi.BX, live_z = 2 * Z % gi.BZ;         // pre-pool extent of the cut column / layer
+  if (live_x) {
+    const MidWalk c = {cdiv(live_x, gx.BX), cdiv(2 * Y, gx.BY), cdiv(2 * Z, gx.BZ), 0, (in.nbx - 1) * gi.BX};
+    if (c.blocks() < (int64_t)in.nby * in.nbz) { xc = c; --in.nbx; }
+  }
+  if (live_z && in.nbx) {
+    const MidWalk c = {in.nbx, cdiv(2 * Y, gz.BY), cdiv(live_z, gz.BZ), (in.nbz - 1) * gi.BZ, 0};
+    if (c.blocks() < (int64_t)in.nbx * in.nby) { zl = c; --in.nbz; }
+  }
+  return p;
+}

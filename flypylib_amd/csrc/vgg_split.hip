@@ -25,6 +25,7 @@
 #define FPL_F16 1   // the operand halves are IEEE halves (mfma_util.h, pack_weights.h)
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 
 #include "fast_paths.h"
 #include "mfma_util.h"
@@ -935,6 +936,107 @@ __global__ __launch_bounds__(64 * x8::WAVES, 2) void vggs_mid_pool(MidXArgs a) {
   ovf_commit(ovf_all, a.flag, FPL_RANGE_MID);
 }
 
+// The blocks of the column / layer that P2 cuts (at 520^3 one of 8 pooled x, one of 4 pooled z: 2 of
+// 16 lanes, 2 of 8 waves of a vggs_mid_pool block), in the orientation whose short axis is the cut
+// one (vgg_plan.h: MID_XCOL, MID_ZLAYER; the host picks per axis, vgg_mid_plan).  A launch of its
+// own, so that vggs_mid_pool stays the code it was.  Everything geometric - the tile gather, the
+// tap table, the lane's and the sub-step's voxel, the store - comes from MidGeo / mid_voxel; the K
+// loop, the tap numbering, the weight fragments and the epilogue are vggs_mid_pool's, so every
+// voxel sees the same sequence of MFMAs and P2 is the same bit for bit.  (MID_XCOL's 16 lanes are
+// a tile row - 6 slots - apart: bank conflicts on its B reads, and its stores are 16-B pieces, for
+// 1 / 129 of the tensor.)
+static_assert(mid_geo(MID_INTERIOR).BZ == x8::BZ && mid_geo(MID_INTERIOR).BY == x8::BY &&
+              mid_geo(MID_INTERIOR).BX == x8::BX && mid_geo(MID_INTERIOR).ZS == x8::ZS, "vgg_plan.h describes x8's block");
+struct MidEdgeArgs {
+  MidXArgs m;                    // m.walk: blocks of the orientation's extent
+  int z0, x0;                    // pre-pool origin of the walk's first block
+};
+
+template <int O>
+__global__ __launch_bounds__(64 * x8::WAVES, 2) void vggs_mid_pool_edge(MidEdgeArgs e) {
+  constexpr MidGeo G = mid_geo(O);
+  const MidXArgs &a = e.m;
+  unsigned *ktab = reinterpret_cast<unsigned *>(smem + 2 * x8::BUF);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 15, g = lane >> 4;
+  x8::ktab_init_oriented<O>(ktab, tid);
+  const x8::TileDma td = x8::tile_dma_init_oriented<O>(wave, lane, a.p1.Y, a.p1.XP, (unsigned)a.p1.part_bytes());
+  const int S = (int)gridDim.x >> 3, nbricks = a.walk.bricks();
+  const int group = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3;
+  x8::Cursor cur;
+  if (!x8::cursor_first(a.walk, nbricks, group, slot, S, cur)) return;
+  const int64_t part = a.p1.part_bytes();
+  auto origin = [&](const x8::Cursor &q) {
+    return a.p1.p + a.p1.vox(e.z0 + G.BZ * q.bz, G.BY * q.by, e.x0 + G.BX * q.bx) * 16;
+  };
+  const MidVox v0 = mid_voxel(O, wave, 0, c);
+  const unsigned vb = (unsigned)(G.slot(v0.z, v0.y, v0.x) * 16);
+  auto sub_off = [](int sub) -> unsigned {
+    const MidVox d = mid_voxel(O, 0, sub, 0);
+    return (unsigned)(mid_geo(O).slot(d.z, d.y, d.x) * 16);
+  };
+  unsigned ovf_all = 0u;
+  x8::prime(smem, td, origin(cur), part, a.w3, wave, lane);
+  for (;;) {
+    x8::Cursor nxt = cur;
+    const bool has_next = x8::cursor_next(a.walk, slot, S, nxt);
+    // (block-invariant loads stay inside the block loop: see vggs_mid_pool)
+    int zero = 0;
+    asm volatile("" : "+s"(zero));
+    f32x4 acc[4][3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const f32x4 sh = *reinterpret_cast<const f32x4 *>(a.shift3 + zero + 16 * b + 4 * g);
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub) acc[sub][b] = sh;
+    }
+    x8::conv_block(smem, ktab + 8 * g, td, origin(cur), origin(has_next ? nxt : cur), part, a.w3, vb,
+                   sub_off, wave, lane, acc);
+    asm volatile("" : "+s"(zero));
+    const h16x8 *w4p = a.w4 + zero;
+    f32x4 sh4[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sh4[b][r] = a.shift4[zero + x8::out_channel(b, g, r)];
+    h16x8 w4[3][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) w4[b][s] = w4p[(s * 3 + b) * 64 + lane];
+    f32x4 pooled[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    unsigned ovf = 0u;
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) {
+      const Frag2 h0 = pack_relu_split(acc[sub][0], acc[sub][1], ovf);
+      const h16x8 hx = pack_relu_split_x(acc[sub][2], ovf);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const f32x4 a4 = chain48(w4[b], h0, hx, sh4[b]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pooled[b][r] = __builtin_fmaxf(pooled[b][r], a4[r]);
+      }
+    }
+    // the lane pair c, c ^ 1 holds the window's two halves along the lanes' axis
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        pooled[b][r] = __builtin_fmaxf(pooled[b][r], __shfl_xor(pooled[b][r], 1));
+    // (pre-pool coordinates of sub-step 0 of an even lane are even)
+    const int pz = (e.z0 + G.BZ * cur.bz + v0.z) >> 1, py = (G.BY * cur.by + v0.y) >> 1,
+              px = (e.x0 + G.BX * cur.bx + v0.x) >> 1;
+    const bool inside = pz < a.p2.Z && py < a.p2.Y && px < a.p2.X;
+    if ((c & 1) == 0 && inside)
+      x8::store12(a.p2, a.p2.vox(pz, py, px), g, pooled, ovf);
+    ovf_all = pk_max_i16(ovf_all, inside ? ovf : 0u);
+    if (!has_next) break;
+    cur = nxt;
+  }
+  ovf_commit(ovf_all, a.flag, FPL_RANGE_MID);
+}
+
 // -------------------------------------------------------------------------------
 // The head both tail kernels run on their conv3 accumulators, in registers: ReLU + split,
 // conv1 48->96, conv1 96->96, conv1 96->1 -> the logit of each of the wave's 4 x 16 coarse voxels
@@ -1518,6 +1620,10 @@ int split_prepare(fpl_ctx *ctx, fpl_program *prog, SplitState **out) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_mid_pool,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, x8::SMEM));
+  FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_mid_pool_edge<MID_XCOL>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, x8::SMEM));
+  FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_mid_pool_edge<MID_ZLAYER>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, x8::SMEM));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_c5_tail_p24,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, M_SMEM));
   FPL_HIP(ctx, hipFuncSetAttribute((const void *)vggs_c5_tail,
@@ -1714,8 +1820,9 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
   const VggSlab s = vgg_slab(dims, origins[0], out_sz[0], zb, ze, 7);
   if (s.empty) return 0;   // no valid output voxel
   const VggPyramid py(s.CY), px(s.CX);
-  // FPL_VGG_EDGE_BLOCKS=0: the stem walks its partial blocks in full, as every block (same
-  // results, bit for bit: an A/B switch for tests and timing)
+  // FPL_VGG_EDGE_BLOCKS=0: the stem walks its partial blocks in full, as every block, and the mid
+  // kernel every block in its interior orientation in one launch (same results, bit for bit: an
+  // A/B switch for tests and timing)
   const char *edge_env = getenv("FPL_VGG_EDGE_BLOCKS");
   const int edge_blocks = edge_env ? atoi(edge_env) != 0 : 1;
   FPL_REQUIRE(ctx, (int64_t)S_TZ * SY * SX < ((int64_t)1 << 31),
@@ -1790,9 +1897,26 @@ int fpl_split_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src, int
       a.shift3 = S + st->off_s[2]; a.shift4 = S + st->off_s[3];
       a.p2 = p2;
       a.flag = flag;
-      a.walk = x8::Walk{(int)ceil_div64(px.P2, 8), (int)ceil_div64(py.P2, 2), (int)ceil_div64(pz.P2, 4)};
+      // the column / layer that P2 cuts goes to launches of its own orientation where that takes
+      // fewer blocks (vgg_mid_plan); one timing entry for all of them
+      const MidPlan mp = vgg_mid_plan(pz.P2, py.P2, px.P2, edge_blocks != 0);
+      auto walk_of = [&](int o) { return x8::Walk{mp.w[o].nbx, mp.w[o].nby, mp.w[o].nbz}; };
       TimedLaunch tl(ctx, "vggs_mid_pool");
-      vggs_mid_pool<<<pgrid, 64 * x8::WAVES, x8::SMEM, stream>>>(a);
+      if (mp.w[MID_INTERIOR].blocks()) {
+        a.walk = walk_of(MID_INTERIOR);
+        vggs_mid_pool<<<pgrid, 64 * x8::WAVES, x8::SMEM, stream>>>(a);
+      }
+      for (int o : {MID_XCOL, MID_ZLAYER}) {
+        if (!mp.w[o].blocks()) continue;
+        MidEdgeArgs e = {a, mp.w[o].z0, mp.w[o].x0};
+        e.m.walk = walk_of(o);
+        // one workgroup per block at most, still a multiple of the 8 XCD groups of the walk
+        const unsigned egrid = (unsigned)std::min<int64_t>(pgrid, (mp.w[o].blocks() + 7) / 8 * 8);
+        if (o == MID_XCOL)
+          vggs_mid_pool_edge<MID_XCOL><<<egrid, 64 * x8::WAVES, x8::SMEM, stream>>>(e);
+        else
+          vggs_mid_pool_edge<MID_ZLAYER><<<egrid, 64 * x8::WAVES, x8::SMEM, stream>>>(e);
+      }
     }
     {
       TailXArgs a;

@@ -33,6 +33,7 @@
 // seven; 27 taps x 8 channels = 216 of 224 k-slots used).
 #pragma once
 #include "mfma_util.h"
+#include "vgg_plan.h"
 #include "vgg_tiles.h"
 
 namespace x8 {
@@ -104,6 +105,24 @@ __device__ __forceinline__ TileDma tile_dma_init(int wave, int lane, int SY, int
   return d;
 }
 
+// The same for a block in orientation O (vgg_plan.h, MidGeo): its tile takes the first slots() slots
+// of each part plane, the LDS layout and the chunk deal are the interior's.
+template <int O>
+__device__ __forceinline__ TileDma tile_dma_init_oriented(int wave, int lane, int SY, int SX, unsigned part_bytes) {
+  constexpr MidGeo G = mid_geo(O);
+  static_assert(G.slots() <= PLANE, "an oriented tile fits the part plane's slots");
+  TileDma d;
+#pragma unroll
+  for (int i = 0; i < TCH; ++i) {
+    int slot = 64 * (wave + WAVES * i) + lane;
+    slot = slot < 2 * PLANE ? slot : 2 * PLANE - 1;
+    const int part = slot >= PLANE;
+    const MidVox v = mid_slot_voxel(G, slot - part * PLANE);
+    d.off[i] = (unsigned)(((v.z * SY + v.y) * SX + v.x) * 16) + (part ? part_bytes : 0u);
+  }
+  return d;
+}
+
 // Filling a buffer by LDS-DMA: 79 chunks of 1 KiB - the 37 tile chunks, then the 42 weight
 // fragments, contiguous in the buffer - dealt round-robin to the 8 waves: chunk j = wave + 8 i,
 // i = 0 .. 9.  i <= 3 is always a tile chunk, i >= 5 always a weight fragment, i = 4 a tile chunk
@@ -145,6 +164,16 @@ __device__ __forceinline__ void ktab_init(unsigned *ktab, int tid) {
     const int g = tid >> 3, s = tid & 7;
     const int tap = 4 * s + g;
     ktab[tid] = tap < 27 ? (unsigned)(((tap / 9) * ZS + ((tap / 3) % 3) * TX + tap % 3) * 16) : 0u;
+  }
+}
+
+template <int O>
+__device__ __forceinline__ void ktab_init_oriented(unsigned *ktab, int tid) {
+  constexpr MidGeo G = mid_geo(O);
+  if (tid < 32) {
+    const int g = tid >> 3, s = tid & 7;
+    const int tap = 4 * s + g;
+    ktab[tid] = tap < 27 ? (unsigned)(mid_tap_slot(G, tap) * 16) : 0u;
   }
 }
 
