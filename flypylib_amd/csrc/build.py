@@ -1,4 +1,4 @@
-"""Build libfplhip.so for gfx950 (MI355X) with hipcc, in-tree.
+"""Build libfplhip.so and libfplbatch.so for gfx950 (MI355X) with hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -8,6 +8,11 @@ was built from (its source, every header, the compiler flags) matches the stamp 
 to it - modification times say nothing on a tree that ships objects, and the driver's
 build check must compile what it ships.  hipcc cross-compiles without a GPU, so this
 runs in the CPU-only build container.
+
+libfplbatch.so (include/fplbatch.h, the device batch generators) is a library of its own:
+its sources live in csrc/batchgen/, are compiled with the same flags and stamps, and its
+version script exports the fplb_* prefix only - libfplhip.so's export list stays the
+fpl_* names of include/fplhip.h.
 """
 import argparse
 import hashlib
@@ -21,6 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 OBJ_DIR = os.path.join(HERE, 'build')
 LIB_DIR = os.path.join(os.path.dirname(HERE), 'lib')
 LIB = os.path.join(LIB_DIR, 'libfplhip.so')
+BATCH_DIR = os.path.join(HERE, 'batchgen')
+BATCH_LIB = os.path.join(LIB_DIR, 'libfplbatch.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -53,22 +60,24 @@ def _sources():
     return out
 
 
-def _headers_digest():
+def _digest(paths):
     """one digest over every header a translation unit may include"""
-    hs = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith('.h'))
-    hs.append(os.path.join(ROOT, 'include', 'fplhip.h'))
     h = hashlib.sha256()
-    for p in hs:
+    for p in paths:
         h.update(os.path.basename(p).encode() + b'\0')
         h.update(open(p, 'rb').read())
     return h.hexdigest()
 
 
-def _compile(unit, force, hdr_digest):
+def _local_headers(d):
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith('.h'))
+
+
+def _compile(unit, force, hdr_digest, src_dir=HERE):
     src, stem, extra = unit
     obj = os.path.join(OBJ_DIR, stem + '.o')
     stamp = obj + '.sha256'
-    sp = os.path.join(HERE, src)
+    sp = os.path.join(src_dir, src)
     h = hashlib.sha256()
     h.update(open(sp, 'rb').read())
     h.update(hdr_digest.encode())
@@ -89,13 +98,13 @@ def _compile(unit, force, hdr_digest):
     return obj, r.stdout
 
 
-def build(force=False, jobs=4, verbose=True):
+def _build_library(lib, exports, srcs, src_dir, hdr_digest, force, jobs, verbose):
+    """compile `srcs` (stale objects only) and link them into `lib`, whose version script
+    exports the `exports` pattern and nothing else"""
     os.makedirs(OBJ_DIR, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    hdr_m = _headers_digest()
-    srcs = _sources()
     with ThreadPoolExecutor(max_workers=jobs) as ex:
-        results = list(ex.map(lambda s: _compile(s, force, hdr_m), srcs))
+        results = list(ex.map(lambda s: _compile(s, force, hdr_digest, src_dir), srcs))
     objs = [o for o, _ in results]
     rebuilt = [u[1] for u, (_, out) in zip(srcs, results) if out is not None]
     for u, (_, out) in zip(srcs, results):
@@ -106,17 +115,17 @@ def build(force=False, jobs=4, verbose=True):
     for o in objs:
         lh.update(open(o + '.sha256').read().encode())
     lib_want = lh.hexdigest()
-    lib_stamp = LIB + '.sha256'
-    if (rebuilt or not os.path.exists(LIB) or not os.path.exists(lib_stamp)
+    lib_stamp = lib + '.sha256'
+    if (rebuilt or not os.path.exists(lib) or not os.path.exists(lib_stamp)
             or open(lib_stamp).read().strip() != lib_want):
-        # the export list = the C entry points include/fplhip.h declares, nothing else (the
-        # C++ internals are hidden by -fvisibility=hidden, libstdc++'s template instances -
-        # default visibility by their own headers - by this version script)
-        vs = os.path.join(OBJ_DIR, 'exports.map')
+        # the export list = the C entry points the library's header declares, nothing else
+        # (the C++ internals are hidden by -fvisibility=hidden, libstdc++'s template
+        # instances - default visibility by their own headers - by this version script)
+        vs = os.path.join(OBJ_DIR, os.path.basename(lib) + '.map')
         with open(vs, 'w') as f:
-            f.write('{ global: fpl_*; local: *; };\n')
+            f.write('{ global: %s; local: *; };\n' % exports)
         cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-Wl,--version-script=' + vs,
-               '-o', LIB] + objs
+               '-o', lib] + objs
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                            text=True)
         if r.returncode != 0:
@@ -125,10 +134,30 @@ def build(force=False, jobs=4, verbose=True):
             f.write(lib_want + '\n')
         if verbose:
             print('linked %s (%d objects, rebuilt: %s)' % (
-                os.path.relpath(LIB, ROOT), len(objs), ', '.join(rebuilt) or '-'))
+                os.path.relpath(lib, ROOT), len(objs), ', '.join(rebuilt) or '-'))
     elif verbose:
-        print('%s is up to date' % os.path.relpath(LIB, ROOT))
+        print('%s is up to date' % os.path.relpath(lib, ROOT))
+    return lib
+
+
+def build(force=False, jobs=4, verbose=True):
+    inc = os.path.join(ROOT, 'include')
+    _build_library(LIB, 'fpl_*', _sources(), HERE,
+                   _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
+                   force, jobs, verbose)
+    build_batch(force, jobs, verbose)
     return LIB
+
+
+def build_batch(force=False, jobs=4, verbose=True):
+    """libfplbatch.so from csrc/batchgen/*.hip: same flags, same SHA-stamped rebuild, a
+    version script that exports fplb_* only"""
+    inc = os.path.join(ROOT, 'include')
+    srcs = [(f, 'batchgen_' + f[:-4], ['-I' + inc])
+            for f in sorted(os.listdir(BATCH_DIR)) if f.endswith('.hip')]
+    return _build_library(BATCH_LIB, 'fplb_*', srcs, BATCH_DIR,
+                          _digest(_local_headers(BATCH_DIR) + [os.path.join(inc, 'fplbatch.h')]),
+                          force, jobs, verbose)
 
 
 if __name__ == '__main__':

@@ -188,7 +188,49 @@ def _load_main(src):
     return keras_io.read_main(src)
 
 
-def gen_batches(train_data, context_sz, batch_sz, is_mask=False, rng=None):
+_DEVICE_DOC = """
+
+    device=None (default) is the host generator.  device=<int> or True (the runtime's
+    default device) selects device mode: the volumes are uploaded once, the host only draws
+    the random numbers, and one HIP kernel per batch cuts and augments it
+    (batchgen.DeviceBatches).  The batches are bit-identical to the host generator's for
+    the same `rng`, but are contiguous torch CUDA tensors taken from a ring of `ring`
+    buffer pairs: a batch is valid until `ring - 1` further batches have been drawn.
+    Input the device mode does not take raises ValueError at the call; without torch, a
+    GPU or libfplbatch.so the call raises - there is no silent host fallback."""
+
+
+def _batches_volumes(train_data, half):
+    """(image, labels, mask) per training volume of gen_batches, the mask cleared where a
+    patch would not fit: entries are (image, labels_prefix) h5 paths as in the reference
+    or (image, labels, mask) arrays.  Labels and mask are copies; the host generator and
+    its planner (batchgen.BatchesPlanner) both start from this."""
+    vols = []
+    for tr in train_data:
+        if len(tr) == 3:
+            im, ll, mm = (np.array(_load_main(a)) for a in tr)
+        else:
+            im = _load_main(tr[0])
+            ll = np.array(_load_main('%slabels.h5' % tr[1]))
+            mm = np.array(_load_main('%smask.h5' % tr[1]))
+        for ax in range(3):                      # patches must fit in the volume
+            sl = [slice(None)] * 3
+            sl[ax] = slice(0, half[ax]); mm[tuple(sl)] = 0
+            sl[ax] = slice(-half[ax], None); mm[tuple(sl)] = 0
+        vols.append((im, ll, mm))
+    return vols
+
+
+def gen_batches(train_data, context_sz, batch_sz, is_mask=False, rng=None, device=None,
+                ring=6):
+    if device is not None:
+        from . import batchgen
+        return batchgen.device_generator('batches', device, ring, train_data, context_sz,
+                                         batch_sz, is_mask, rng)
+    return _gen_batches_host(train_data, context_sz, batch_sz, is_mask, rng)
+
+
+def _gen_batches_host(train_data, context_sz, batch_sz, is_mask=False, rng=None):
     """generator of balanced training batches (reference fplobjdetect.py:27-130).
 
     train_data: sequence of (image, labels_prefix) as in the reference (h5 paths;
@@ -203,17 +245,7 @@ def gen_batches(train_data, context_sz, batch_sz, is_mask=False, rng=None):
     half = tuple(int(round(cc / 2)) for cc in context_sz)
 
     vols = []
-    for tr in train_data:
-        if len(tr) == 3:
-            im, ll, mm = (np.array(_load_main(a)) for a in tr)
-        else:
-            im = _load_main(tr[0])
-            ll = np.array(_load_main('%slabels.h5' % tr[1]))
-            mm = np.array(_load_main('%smask.h5' % tr[1]))
-        for ax in range(3):                      # patches must fit in the volume
-            sl = [slice(None)] * 3
-            sl[ax] = slice(0, half[ax]); mm[tuple(sl)] = 0
-            sl[ax] = slice(-half[ax], None); mm[tuple(sl)] = 0
+    for im, ll, mm in _batches_volumes(train_data, half):
         centres = [((ll == cc) & (mm == 1)).nonzero() for cc in range(2)]
         if is_mask:
             ll[mm == 0] = 2
@@ -372,7 +404,15 @@ def get_out_sz(in_sz):
     return (bottleneck_sz * 2 - 2) * 2 - 2
 
 
-def gen_volume(train_data, context_sz, batch_sz, ratio, rng=None):
+def gen_volume(train_data, context_sz, batch_sz, ratio, rng=None, device=None, ring=6):
+    if device is not None:
+        from . import batchgen
+        return batchgen.device_generator('volume', device, ring, train_data, context_sz,
+                                         batch_sz, ratio, rng)
+    return _gen_volume_host(train_data, context_sz, batch_sz, ratio, rng)
+
+
+def _gen_volume_host(train_data, context_sz, batch_sz, ratio, rng=None):
     """generator of training batches with dense 6^3 labels (reference
     fplobjdetect.py:536-658; what scripts/fpl_cx1_0_unet_4ss_all.py:41-42 trains
     unet_like2 with): example i of a batch comes from volume i mod n_volumes, centred
@@ -447,7 +487,16 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
     return aggregate_pr(results), results
 
 
-def gen_volume2(train_data, context_sz, batch_sz, ratio, noise_aug=[0, 0], rng=None):
+def gen_volume2(train_data, context_sz, batch_sz, ratio, noise_aug=[0, 0], rng=None,
+                device=None, ring=6):
+    if device is not None:
+        from . import batchgen
+        return batchgen.device_generator('volume2', device, ring, train_data, context_sz,
+                                         batch_sz, ratio, noise_aug, rng)
+    return _gen_volume2_host(train_data, context_sz, batch_sz, ratio, noise_aug, rng)
+
+
+def _gen_volume2_host(train_data, context_sz, batch_sz, ratio, noise_aug=[0, 0], rng=None):
     """generator of training batches with dense 6^3 labels for the U-Nets (reference
     fplobjdetect.py:660-822): `ratio` of each outer round of 100 batches is centred on
     label-0 voxels, the rest on label-1 voxels, drawn from all volumes (optionally
@@ -525,6 +574,12 @@ def gen_volume2(train_data, context_sz, batch_sz, ratio, noise_aug=[0, 0], rng=N
                         v = np.flipud(v)
                     a[ii, :, :, :, 0] = v
             yield data.copy(), labels.copy()
+
+
+for _f, _h in ((gen_batches, _gen_batches_host), (gen_volume, _gen_volume_host),
+               (gen_volume2, _gen_volume2_host)):
+    _f.__doc__ = _h.__doc__ + _DEVICE_DOC
+del _f, _h
 
 
 def write_sampling_weights(train_data, network, fn_prefix, l0_thresh, l1_thresh):

@@ -215,7 +215,11 @@ def setup_rank_comm(ctx, dist=None):
 # ---- towers of one process ----------------------------------------------------------
 class TowerGroup:
     """`n` trainers, one host thread each, stepping in lockstep on slices of one
-    batch (the single-process form of make_train_parallel)"""
+    batch (the single-process form of make_train_parallel).
+
+    The towers sit on several GPUs, so batches reach them as host arrays: a device batch
+    generator (`gen_*(device=...)`) is taken through the host here (`.cpu().numpy()` in
+    `_Prefetch`) - the correct path, not the fast one.  One process per GPU is the fast one."""
 
     def __init__(self, graph, devices, loss, opt_args):
         self.n = len(devices)
@@ -403,7 +407,10 @@ class _Prefetch:
                 if self._stage is not None:
                     item = self._stage(*item)     # its own copies, already on the GPU
                 else:
-                    item = tuple(np.array(a) for a in item)
+                    # device batches (gen_*(device=...)) reach host consumers through the
+                    # host: correct, not fast
+                    item = tuple(a.cpu().numpy() if getattr(a, 'is_cuda', False)
+                                 else np.array(a) for a in item)
                 if not self._put(item):
                     return
             self._put(StopIteration())
@@ -450,6 +457,15 @@ class _DeviceStager:
             raise ValueError(self._need_msg % data.shape[0])
         if self._rows is not None:
             data, labels = data[self._rows], labels[self._rows]
+        if getattr(data, 'is_cuda', False) and getattr(labels, 'is_cuda', False):
+            # a device batch generator (batchgen.DeviceBatches): already complete on the
+            # GPU, passed through without a copy (a row slice of a contiguous tensor is
+            # contiguous); its ring keeps it alive long enough, see fit_generator
+            if data.device != self._dev or labels.device != self._dev:
+                raise ValueError('the batch generator cuts its batches on %s, the trainer is on '
+                                 '%s: give gen_*(device=...) the trainer\'s device'
+                                 % (data.device, self._dev))
+            return data, labels
         x = np.ascontiguousarray(data, np.float32)
         y = np.ascontiguousarray(labels, np.uint8)
         with torch.cuda.stream(self._stream):
@@ -556,6 +572,16 @@ def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
                       '%d examples, got %%d' % (world, par.batch_size, need))
         else:
             stage = _DeviceStager(trainer.ctx.device)
+    # A device batch generator hands out ring buffers, valid until ring - 1 further batches
+    # are drawn.  With _Prefetch's depth of 2, while the training thread steps on batch n
+    # the queue can hold n+1 and n+2 and the worker n+3, blocked in put().  When the step
+    # of n is over (metrics() has read it back) the thread takes n+1, the worker's put of
+    # n+3 succeeds and it draws n+4: live at that moment are n+1 (in use), n+2, n+3 (queued)
+    # and n+4 (being written) - four.  n+4 may reuse n's buffers, so ring >= 4.
+    ring = getattr(generator, 'ring', None)
+    if ring is not None and ring < 4:
+        raise ValueError('device batch generator with ring=%d: fit_generator prefetches 2 '
+                         'batches ahead and needs ring >= 4' % ring)
     batches = _Prefetch(generator, stage=stage)
     try:
         for epoch in range(epochs):

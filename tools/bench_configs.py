@@ -18,6 +18,11 @@
             (2 of 13 tile rows + halo), bit-compared with the same rows of a whole-volume run
   c5share   configs[4] at its stated size: rank 0's 64 of the 512 substacks of a 4096^3
             synthetic ROI, one substack diffed against the CPU oracle
+  train_gen the training loops fed three ways in one process: (a) the constant batch of
+            the `train` / `train_unet` rows, (b) the host generator, (c) the device generator
+            (gen_batches(device=...) for vgg_like 32 x 64^3, gen_volume2(device=...) with noise
+            for unet_like2 64 x 24^3), through fit_generator's prefetch loop; plus the planner's
+            ms per batch and the gather kernel's ms (HIP events), rot 0 and rot 1 separately
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -31,6 +36,112 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def train_gen(ctx, torch, steps=30, vol=200):
+    """ms/step of the training loop fed by a constant batch, the host generator and the
+    device generator (same process, same trainer), on synthetic volumes"""
+    from flypylib_amd import _capi, fplmodels, fplobjdetect, synth, train as fpl_train
+    shape = (vol,) * 3
+    im = synth.em_volume_u8(31, shape).astype(np.float32)
+    ll = (synth.hash_uniform_f32(131, shape) > np.float32(0.97)).astype(np.uint8)
+    train_data = [(im, ll, np.ones(shape, np.uint8))]
+    out = {'volume': list(shape), 'image_dtype': 'float32', 'steps': steps}
+
+    def loop(tr, gen):
+        # fit_generator's loop without its CSV bookkeeping and metrics() call: the same
+        # _Prefetch (depth 2) and _DeviceStager.  The ring of a device generator is safe here
+        # for the reason it is there: Trainer.step returns (loss, accuracy), which it reads
+        # back from the device, so the step has consumed its batch before the next is taken.
+        # The vgg loops train on a constant 12^3 label block (see the DESIGN.md section), so
+        # what differs between the three loops is the cutting of the data alone.
+        batches = fpl_train._Prefetch(gen, stage=fpl_train._DeviceStager(ctx.device))
+        try:
+            for s in range(3):
+                tr.step(*next(batches), s); tr.apply(1.0)
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for s in range(steps):
+                tr.step(*next(batches), s + 3); tr.apply(1.0)
+            ctx.synchronize()
+            return (time.perf_counter() - t0) / steps * 1e3
+        finally:
+            batches.close()
+
+    def constant(batch):
+        while True:
+            yield batch
+
+    def kernel_ms(make_dev, rot):
+        """the gather kernel alone, every example of the batch with one rot"""
+        dev = make_dev()
+        draw = dev.plan.records
+
+        def forced():
+            rec = draw()
+            rec['rot'] = rot
+            return rec
+        dev.plan.records = forced
+        dev.time_kernel = True
+        for _ in range(13):
+            next(dev)
+        return float(np.median(dev.kernel_ms[3:]))
+
+    # vgg_like, 32 x 64^3.  gen_batches labels a patch by its centre voxel (or 6^3 around it);
+    # on a 64^3 patch vgg_like's output is 12^3, so - as in the constant-batch rows - the
+    # labels are a constant 12^3 block and the generators supply the data, which is all but
+    # 32 bytes of what they move.
+    g = fplmodels.vgg_like()[0]
+    synth.synthetic_weights(g, 8)
+    tr = _capi.Trainer(ctx, g)
+    rng = np.random.default_rng(0)
+    lab12 = (rng.random((32, 12, 12, 12)) > 0.9).astype(np.uint8)
+    lab12_dev = torch.from_numpy(lab12).to('cuda:%d' % ctx.device)
+    data = rng.standard_normal((32, 64, 64, 64)).astype(np.float32)
+
+    def data_of(gen, labels):
+        for d, _ in gen:
+            yield d, labels
+    mk = lambda **kw: fplobjdetect.gen_batches(train_data, 64, 32, rng=np.random.RandomState(0), **kw)  # noqa: E731
+    dev = mk(device=ctx.device)
+    r = {'constant_ms': loop(tr, constant((data, lab12))),
+         'host_gen_ms': loop(tr, data_of(mk(), lab12)),
+         'device_gen_ms': loop(tr, data_of(dev, lab12_dev))}
+    r['planner_ms_per_batch'] = dev.plan_seconds / dev.batches * 1e3
+    moved = 32 * 64 ** 3 * 8
+    for rot in (0, 1):
+        ms = kernel_ms(lambda: mk(device=ctx.device), rot)
+        r['gather_rot%d_ms' % rot] = ms
+        r['gather_rot%d_gb_s' % rot] = moved / ms / 1e6
+    r['device_over_constant'] = r['device_gen_ms'] / r['constant_ms']
+    r['host_over_device'] = r['host_gen_ms'] / r['device_gen_ms']
+    out['vgg_like_b32_64cubed'] = {k: round(v, 4) for k, v in r.items()}
+    print(json.dumps(out['vgg_like_b32_64cubed']), flush=True)
+    tr.close()
+
+    # unet_like2, 64 x 24^3, gen_volume2 with noise on: data and 6^3 labels from the generator
+    g = fplmodels.unet_like2()[0]
+    synth.synthetic_weights(g, 3)
+    tr = _capi.Trainer(ctx, g, loss='masked_focal_loss')
+    data = rng.standard_normal((64, 24, 24, 24, 1)).astype(np.float32)
+    labels = rng.integers(0, 3, (64, 6, 6, 6, 1)).astype(np.uint8)
+    mk = lambda **kw: fplobjdetect.gen_volume2(train_data, 24, 64, 0.5, noise_aug=[0.05, 0.1],  # noqa: E731
+                                               rng=np.random.RandomState(0), **kw)
+    dev = mk(device=ctx.device)
+    r = {'constant_ms': loop(tr, constant((data, labels))),
+         'host_gen_ms': loop(tr, mk()),
+         'device_gen_ms': loop(tr, dev)}
+    r['planner_ms_per_batch'] = dev.plan_seconds / dev.batches * 1e3
+    moved = 64 * 24 ** 3 * 8
+    for rot in (0, 1):
+        ms = kernel_ms(lambda: mk(device=ctx.device), rot)
+        r['gather_rot%d_ms' % rot] = ms
+        r['gather_rot%d_gb_s' % rot] = moved / ms / 1e6
+    r['device_over_constant'] = r['device_gen_ms'] / r['constant_ms']
+    r['host_over_device'] = r['host_gen_ms'] / r['device_gen_ms']
+    out['unet_like2_b64_24cubed'] = {k: round(v, 4) for k, v in r.items()}
+    tr.close()
+    return out
 
 
 def main():
@@ -217,6 +328,10 @@ def main():
             kernels={k: round(v['ms'] / steps, 3) for k, v in ctx.timing_get().items()})
         ctx.timing(False)
         print(json.dumps(res['unet_train_b64_24cubed_f32']), flush=True)
+
+    if 'train_gen' in what:
+        res['train_gen'] = train_gen(ctx, torch)
+        print(json.dumps(res['train_gen']), flush=True)
 
     if 'v2o' in what or 'pipeline' in what:
         n = a.sub

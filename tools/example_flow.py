@@ -42,6 +42,9 @@ def main(argv=None):
     ap.add_argument('--epochs', type=int, default=2)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--device-batches', action='store_true',
+                    help='cut and augment the training batches on the GPU '
+                         '(gen_volume2(device=True)): same batches, bit for bit')
     a = ap.parse_args(argv)
     data_dir = a.out or tempfile.mkdtemp(prefix='fpl_example_')
     os.makedirs(data_dir, exist_ok=True)
@@ -62,7 +65,8 @@ def main(argv=None):
     train_data = [['%s/0_im.npy' % data_dir, '%s/0_labels.npy' % data_dir,
                    '%s/0_mask.npy' % data_dir]]
     generator = fplobjdetect.gen_volume2(train_data, network.rf_size, a.batch, 0.5,
-                                         rng=np.random.RandomState(0))
+                                         rng=np.random.RandomState(0),
+                                         device=True if a.device_batches else None)
     network.train(generator, a.steps, a.epochs, '%s/log.csv' % data_dir, '%s/epoch' % data_dir)
     network.save_network('%s/net' % data_dir)
 
