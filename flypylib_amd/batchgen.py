@@ -172,24 +172,43 @@ class Volume2Planner(_Planner):
     second_flip = _FLIP1          # np.fliplr
     noise = True                  # the host always computes m * v + a, also for [0, 0]
 
-    def __init__(self, train_data, context_sz, batch_sz, ratio, noise_aug=(0, 0), rng=None):
+    def __init__(self, train_data, context_sz, batch_sz, ratio, noise_aug=(0, 0), rng=None,
+                 tables=None, device=None):
+        """tables=None: the candidate tables come from numpy's nonzero(), as in the host
+        generator.  tables='device': from libfplmine.so's compaction on GPU `device` -
+        labels, mask and weights are uploaded once (resident tensors are kept), only the
+        compacted rows come back, and `images` / `labels` of the plan are left resident for
+        DeviceBatches.  A callable `tables(labels, mask, half, cc, weights) -> (z, y, x, w)`
+        (mine.candidates_numpy) is used in place of nonzero() on the host volumes."""
         super().__init__(context_sz, batch_sz, rng)
         self.ratio, self.noise_aug = ratio, noise_aug
-        vols = fplobjdetect._volumes(train_data, self.half)
+        if tables == 'device':
+            vols, rows = self._device_volumes(train_data, device)
+        elif tables is None or callable(tables):
+            vols = fplobjdetect._volumes(train_data, self.half)
+            rows = tables
+        else:
+            raise ValueError("tables=%r: None, 'device' or a callable" % (tables,))
         weighted = vols[0][3] is not None
         self._p, cols_all, self._n = [], [[], [], [], []], []
         for cc in range(2):
             cols = [[], [], [], [], []]
             for vi, (im, ll, mm, ww) in enumerate(vols):
-                sel = (ll == cc) & (mm == 1)
-                if weighted:
-                    sel &= ww > 0
-                idx = sel.nonzero()
+                if rows is None:
+                    sel = (ll == cc) & (mm == 1)
+                    if weighted:
+                        sel &= ww > 0
+                    idx = sel.nonzero()
+                    w = ww[idx] if weighted else None
+                else:
+                    if weighted and ww is None:
+                        raise ValueError('volume %d has no weights, volume 0 has' % vi)
+                    *idx, w = rows(ll, mm, self.half, cc, ww if weighted else None)
                 cols[0].append(np.full(idx[0].shape, vi, np.int32))
                 for a in range(3):
                     cols[1 + a].append(idx[a].astype(np.int32))
                 if weighted:
-                    cols[4].append(ww[idx].astype(np.float64))
+                    cols[4].append(w.astype(np.float64))
             cols = [np.concatenate(c) if c else None for c in cols]
             if weighted:
                 cols[4] = cols[4] / np.sum(cols[4].astype('float32'))
@@ -200,7 +219,37 @@ class Volume2Planner(_Planner):
         self._cols = [np.concatenate(c) for c in cols_all]     # class 0 rows, then class 1
         for im, ll, mm, ww in vols:
             self.images.append(im)
-            self.labels.append(_masked_labels(ll, mm))
+            self.labels.append(self._masked(ll, mm) if tables == 'device'
+                               else _masked_labels(ll, mm))
+
+    def _device_volumes(self, train_data, device):
+        """(image, labels, mask, weights) per volume with labels, mask and weights resident
+        (uint8 / uint8 / float32 tensors) and the compaction that reads them.  The mask is
+        left as it is: the kernels and `_masked` apply the `half` border themselves."""
+        from . import mine
+        if device is None:
+            raise ValueError("tables='device' needs the GPU to build them on (device=...)")
+        dev = mine.torch_device(device)
+        vols = []
+        for tr in train_data:
+            if isinstance(tr[1], str) and not tr[1].endswith('.npy'):
+                tr = [tr[0], '%slabels.h5' % tr[1], '%smask.h5' % tr[1]] + list(tr[2:])
+            im, ll, mm, ww = (a if a is None or mine.is_device_tensor(a)
+                              else fplobjdetect._load_main(a)
+                              for a in (list(tr[:4]) + [None])[:4])
+            vols.append((im, mine.to_device_u8(ll, dev), mine.to_device_u8(mm, dev),
+                         None if ww is None else mine.to_device_f32(ww, dev)))
+        self._dev = dev
+        return vols, mine.candidates_device
+
+    def _masked(self, ll, mm):
+        """_masked_labels on resident tensors: 2 where the mask, cleared inside the `half`
+        border as `_volumes` clears it, is 0"""
+        import torch
+        keep = torch.zeros_like(mm, dtype=torch.bool)
+        h, d = self.half, mm.shape
+        keep[h[0]:d[0] - h[0], h[1]:d[1] - h[1], h[2]:d[2] - h[2]] = True
+        return torch.where(keep & (mm != 0), ll, torch.full_like(ll, 2))
 
     def _draw(self):
         B, rng = self.batch_sz, self.rng
@@ -274,9 +323,33 @@ def planned_batches(plan):
         yield execute_numpy(plan, plan.records())
 
 
+def _np_dtype(a):
+    """numpy dtype of an array or a torch tensor"""
+    if isinstance(a, np.ndarray):
+        return a.dtype
+    if hasattr(a, 'is_cuda'):
+        return np.dtype(str(a.dtype).replace('torch.', ''))
+    return np.asarray(a).dtype
+
+
+def _is_resident(a, dev):
+    return hasattr(a, 'is_cuda') and bool(a.is_cuda) and a.device == dev
+
+
+def volume2_tables(train_data, tables):
+    """the `tables` argument gen_volume2's device mode hands its planner: 'device' when asked
+    for, or when labels, mask or weights of an entry are torch CUDA tensors"""
+    if tables is not None:
+        return tables
+    for tr in train_data:
+        if any(hasattr(a, 'is_cuda') and a.is_cuda for a in tr[1:4]):
+            return 'device'
+    return None
+
+
 def check_image_dtypes(plan):
     """device mode keeps float32 and uint8 images in their own dtype; anything else is refused"""
-    kinds = {np.dtype(np.asarray(im).dtype) for im in plan.images}
+    kinds = {np.dtype(_np_dtype(im)) for im in plan.images}
     for k in kinds:
         if k not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError('device batches take float32 or uint8 images, not %s (use the '
@@ -328,9 +401,12 @@ class DeviceBatches:
         self._dev = dev = torch.device('cuda', device)
         self._src_dtype = src_dtype
         want = np.float32 if src_dtype == _batchcapi.F32 else np.uint8
-        self._images = [torch.from_numpy(np.ascontiguousarray(im, want)).to(dev)
+        # what a planner left resident on this device is not uploaded a second time
+        self._images = [im.contiguous() if _is_resident(im, dev)
+                        else torch.from_numpy(np.ascontiguousarray(im, want)).to(dev)
                         for im in plan.images]
-        self._labels = [torch.from_numpy(np.ascontiguousarray(ll).astype(np.uint8)).to(dev)
+        self._labels = [ll.contiguous() if _is_resident(ll, dev)
+                        else torch.from_numpy(np.ascontiguousarray(ll).astype(np.uint8)).to(dev)
                         for ll in plan.labels]
         table = np.zeros(len(self._images), _batchcapi.VOLUME)
         for i, (im, ll) in enumerate(zip(self._images, self._labels)):
@@ -408,4 +484,6 @@ def device_generator(kind, device, ring, *args, **kw):
     torch, a GPU or the library) - there is no silent host fallback"""
     planner = {'batches': BatchesPlanner, 'volume': VolumePlanner,
                'volume2': Volume2Planner}[kind]
+    if kw.get('tables') == 'device':         # gen_volume2: the tables are built on that GPU too
+        kw['device'] = device
     return DeviceBatches(planner(*args, **kw), device, ring)

@@ -1,4 +1,4 @@
-"""Build libfplhip.so and libfplbatch.so for gfx950 (MI355X) with hipcc, in-tree.
+"""Build libfplhip.so, libfplbatch.so and libfplmine.so for gfx950 (MI355X) with hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -12,7 +12,8 @@ runs in the CPU-only build container.
 libfplbatch.so (include/fplbatch.h, the device batch generators) is a library of its own:
 its sources live in csrc/batchgen/, are compiled with the same flags and stamps, and its
 version script exports the fplb_* prefix only - libfplhip.so's export list stays the
-fpl_* names of include/fplhip.h.
+fpl_* names of include/fplhip.h.  libfplmine.so (include/fplmine.h, hard-example mining:
+csrc/mine/, prefix fplm_*) is built the same way.
 """
 import argparse
 import hashlib
@@ -28,6 +29,8 @@ LIB_DIR = os.path.join(os.path.dirname(HERE), 'lib')
 LIB = os.path.join(LIB_DIR, 'libfplhip.so')
 BATCH_DIR = os.path.join(HERE, 'batchgen')
 BATCH_LIB = os.path.join(LIB_DIR, 'libfplbatch.so')
+MINE_DIR = os.path.join(HERE, 'mine')
+MINE_LIB = os.path.join(LIB_DIR, 'libfplmine.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -146,6 +149,7 @@ def build(force=False, jobs=4, verbose=True):
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
     build_batch(force, jobs, verbose)
+    build_mine(force, jobs, verbose)
     return LIB
 
 
@@ -157,6 +161,16 @@ def build_batch(force=False, jobs=4, verbose=True):
             for f in sorted(os.listdir(BATCH_DIR)) if f.endswith('.hip')]
     return _build_library(BATCH_LIB, 'fplb_*', srcs, BATCH_DIR,
                           _digest(_local_headers(BATCH_DIR) + [os.path.join(inc, 'fplbatch.h')]),
+                          force, jobs, verbose)
+
+
+def build_mine(force=False, jobs=4, verbose=True):
+    """libfplmine.so from csrc/mine/*.hip, as build_batch; exports fplm_* only"""
+    inc = os.path.join(ROOT, 'include')
+    srcs = [(f, 'mine_' + f[:-4], ['-I' + inc])
+            for f in sorted(os.listdir(MINE_DIR)) if f.endswith('.hip')]
+    return _build_library(MINE_LIB, 'fplm_*', srcs, MINE_DIR,
+                          _digest(_local_headers(MINE_DIR) + [os.path.join(inc, 'fplmine.h')]),
                           force, jobs, verbose)
 
 

@@ -247,13 +247,26 @@ class FplNetwork:
             image, self.infer_sz, self.rf_offset, **kw)
 
     def voxel_loss(self, image, lm_prefix, l0_thresh=None, l1_thresh=None,
-                   normalize=None):
+                   normalize=None, device=None):
         """per-voxel log loss of the prediction on labelled, unmasked voxels
         (reference :191-220): confident negatives (loss < 0.005) are dropped, losses
         are clamped to the optional [lo, hi] thresholds.  `lm_prefix`: the reference's
         '<prefix>labels.h5' / '<prefix>mask.h5' prefix or a
-        (labels, mask) pair of arrays / .npy paths."""
+        (labels, mask) pair of arrays / .npy paths.
+
+        device=None (default) is the host path: numpy, a float32 ndarray.  device=<int> or
+        True (the runtime's default device) keeps the step on the GPU: the prediction is
+        inferred into device memory (uploaded from the host instead under
+        make_infer_parallel, or when `device` is not the network's GPU), labels and mask are
+        uploaded once (resident uint8 tensors are taken as they are) and one kernel of
+        libfplmine.so writes the loss, returned as a float32 torch tensor on that device.
+        The kernel's log is the double-precision one rounded to float32
+        (mine.voxel_loss_numpy is its specification), numpy's float32 log on the host path
+        is a few ulp off it.  Without torch, a GPU or libfplmine.so the call raises."""
         from .fplobjdetect import _load_main
+        if device is not None:
+            return self._voxel_loss_device(image, lm_prefix, l0_thresh, l1_thresh, normalize,
+                                           device)
         pred = self.infer(image, normalize=normalize)
         if isinstance(lm_prefix, str):
             labels = np.array(_load_main('%slabels.h5' % lm_prefix))
@@ -281,6 +294,41 @@ class FplNetwork:
         pos = (mask == 1) & (labels == 1)
         l1_loss = clamp(-1. * pos * np.log(np.maximum(pred, 1e-8)), l1_thresh, pos)
         return (l0_loss + l1_loss).astype('float32')
+
+    def _voxel_loss_device(self, image, lm_prefix, l0_thresh, l1_thresh, normalize, device):
+        import torch
+        from . import mine
+        from .fplobjdetect import _load_main
+        dev = mine.torch_device(device)
+        if isinstance(lm_prefix, str):
+            labels, mask = (_load_main('%s%s.h5' % (lm_prefix, n)) for n in ('labels', 'mask'))
+        else:
+            labels, mask = (a if mine.is_device_tensor(a) else _load_main(a) for a in lm_prefix)
+        edge = [int(round(cc / 2)) for cc in self.rf_size]
+        if min(edge) < 1:
+            raise ValueError('rf_size %r: the device voxel_loss needs a border of at least one '
+                             'voxel (use device=None)' % (self.rf_size,))
+        if isinstance(image, str):
+            from . import keras_io
+            image = np.load(image) if image.endswith('.npy') else keras_io.read_main(image)
+        image = np.asarray(image)
+        direct = self._parallel is None and dev.index == int(self.infer_network.device)
+        if direct:
+            assert self.infer_network.input_shape[1:-1] == self.infer_sz, \
+                'network input shape does not match expected infer_sz'
+            assert image.ndim == 3, 'image must be (Z,Y,X)'
+            if image.dtype != np.uint8:
+                image = np.ascontiguousarray(image, dtype=np.float32)
+            mean, std = (0.0, 1.0) if normalize is None else normalize
+            pred = torch.empty(image.shape, dtype=torch.float32, device=dev)
+            # returns when the context's stream has finished writing `pred`
+            self.infer_network.program.infer_volume(
+                image, self.infer_sz, self.rf_offset, mean=mean, std=std,
+                precision=_PRECISIONS[self.precision], dst=pred)
+        else:
+            pred = torch.from_numpy(self.infer(image, normalize=normalize)).to(dev)
+        return mine.voxel_loss_device(pred, mine.to_device_u8(labels, dev),
+                                      mine.to_device_u8(mask, dev), edge, l0_thresh, l1_thresh)
 
     # pickling: device handles never travel
     def __getstate__(self):

@@ -197,7 +197,12 @@ _DEVICE_DOC = """
     the same `rng`, but are contiguous torch CUDA tensors taken from a ring of `ring`
     buffer pairs: a batch is valid until `ring - 1` further batches have been drawn.
     Input the device mode does not take raises ValueError at the call; without torch, a
-    GPU or libfplbatch.so the call raises - there is no silent host fallback."""
+    GPU or libfplbatch.so the call raises - there is no silent host fallback.
+
+    gen_volume2 only: with tables='device', or when an entry's labels, mask or weights are
+    torch CUDA tensors (what write_sampling_weights(device=...) appends), the candidate
+    tables are compacted on the GPU by libfplmine.so and only their rows are downloaded;
+    what is resident is not uploaded again.  The draws stay on the host, in the same order."""
 
 
 def _batches_volumes(train_data, half):
@@ -488,11 +493,15 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
 
 
 def gen_volume2(train_data, context_sz, batch_sz, ratio, noise_aug=[0, 0], rng=None,
-                device=None, ring=6):
+                device=None, ring=6, tables=None):
     if device is not None:
         from . import batchgen
         return batchgen.device_generator('volume2', device, ring, train_data, context_sz,
-                                         batch_sz, ratio, noise_aug, rng)
+                                         batch_sz, ratio, noise_aug, rng,
+                                         tables=batchgen.volume2_tables(train_data, tables))
+    if tables is not None:
+        raise ValueError('gen_volume2(tables=%r) needs device=...: the host generator builds '
+                         'its tables with numpy' % (tables,))
     return _gen_volume2_host(train_data, context_sz, batch_sz, ratio, noise_aug, rng)
 
 
@@ -582,17 +591,29 @@ for _f, _h in ((gen_batches, _gen_batches_host), (gen_volume, _gen_volume_host),
 del _f, _h
 
 
-def write_sampling_weights(train_data, network, fn_prefix, l0_thresh, l1_thresh):
+def write_sampling_weights(train_data, network, fn_prefix, l0_thresh, l1_thresh, device=None,
+                           save=True):
     """per-voxel loss of the current network as sampling weights for `gen_volume2`
     (reference :824-839).  Weights are written as '<fn_prefix>%02d.npy' (the
-    reference writes .h5; h5py is not available here) and appended to each entry."""
+    reference writes .h5; h5py is not available here) and appended to each entry.
+
+    device=<int> or True: `network.voxel_loss(..., device=device)` computes the weights on
+    the GPU and each entry gets the resident float32 tensor appended instead of the file
+    name - `gen_volume2(..., device=device)` then builds its candidate tables from it on
+    the device.  save=True (default) still writes the .npy files; save=False (device mode
+    only) skips the download."""
+    if device is None and not save:
+        raise ValueError('write_sampling_weights(save=False) keeps the weights on the GPU only: '
+                         'it needs device=...')
     train_data_aug = []
     for idx, tr in enumerate(train_data):
         loss = network.voxel_loss(tr[0], tr[1] if isinstance(tr[1], str) else tr[1:3],
-                                  l0_thresh, l1_thresh)
+                                  l0_thresh, l1_thresh, **({} if device is None
+                                                           else {'device': device}))
         ww_fn = '%s%02d.npy' % (fn_prefix, idx)
-        np.save(ww_fn, loss)
-        train_data_aug.append(list(tr) + [ww_fn, ])
+        if save:
+            np.save(ww_fn, loss if device is None else loss.cpu().numpy())
+        train_data_aug.append(list(tr) + [ww_fn if device is None else loss, ])
     return train_data_aug
 
 

@@ -23,6 +23,11 @@
             (gen_batches(device=...) for vgg_like 32 x 64^3, gen_volume2(device=...) with noise
             for unet_like2 64 x 24^3), through fit_generator's prefetch loop; plus the planner's
             ms per batch and the gather kernel's ms (HIP events), rot 0 and rot 1 separately
+  mine      hard-example mining at --mine-size^3 (default 520), all in one process:
+            FplNetwork.voxel_loss on the host against device=..., the voxel-loss kernel alone
+            (HIP events; GB/s at 10 B/voxel), and gen_volume2's candidate tables built by
+            Volume2Planner on the host (nonzero) against tables='device' (libfplmine.so), for
+            an unweighted and a mined (weighted) volume; written to profiles/mine.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -144,8 +149,111 @@ def train_gen(ctx, torch, steps=30, vol=200):
     return out
 
 
+def mine_bench(ctx, torch, n=520, reps=5):
+    """the mining step between two training rounds, host path against device path"""
+    from flypylib_amd import FplNetwork, batchgen, fplmodels, mine, synth
+    shape = (n,) * 3
+    dev = torch.device('cuda', ctx.device)
+    u8 = synth.em_volume_u8(41, shape)
+    ll = (synth.hash_uniform_f32(141, shape) > np.float32(0.97)).astype(np.uint8)
+    mm = np.ones(shape, np.uint8)
+    mm[: n // 4, : n // 3, :] = 0
+    net = FplNetwork(fplmodels.vgg_like)
+    synth.synthetic_weights(net.train_single, 1)
+    net.infer_sz = (102,) * 3
+    net._set_infer()
+    norm, l0, l1 = (128.0, 33.0), (0.05, 2.0), (0.1, 0.5)
+    out = {'volume': list(shape), 'voxels': n ** 3, 'reps': reps}
+
+    def timed(fn, k):
+        fn()
+        torch.cuda.synchronize(dev)
+        ts = []
+        for _ in range(k):
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize(dev)
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3, r
+
+    # voxel_loss through the public entry point
+    t_inf, _ = timed(lambda: net.infer(u8, normalize=norm), reps)
+    t_host, loss_host = timed(lambda: net.voxel_loss(u8, (ll, mm), l0, l1, normalize=norm), 1)
+    t_dev, loss_dev = timed(lambda: net.voxel_loss(u8, (ll, mm), l0, l1, normalize=norm,
+                                                   device=ctx.device), reps)
+    ll_d, mm_d = mine.to_device_u8(ll, dev), mine.to_device_u8(mm, dev)
+    t_res, _ = timed(lambda: net.voxel_loss(u8, (ll_d, mm_d), l0, l1, normalize=norm,
+                                            device=ctx.device), reps)
+    diff = np.abs(loss_dev.cpu().numpy() - loss_host)
+    out['voxel_loss'] = dict(infer_host_result_ms=t_inf, host_ms=t_host, device_ms=t_dev,
+                             device_resident_labels_ms=t_res, host_over_device=t_host / t_dev,
+                             max_abs_diff_host_vs_device=float(diff.max()),
+                             voxels_with_loss=int((loss_host > 0).sum()))
+    print(json.dumps(out['voxel_loss']), flush=True)
+    del loss_host, diff
+
+    # the kernel alone on a synthetic float32 prediction that leaves a mined volume: most
+    # negatives confident
+    pred = torch.from_numpy(synth.hash_uniform_f32(241, shape) ** 32).to(dev)
+    loss = torch.empty(shape, dtype=torch.float32, device=dev)
+    edge = [int(round(c / 2)) for c in net.rf_size]
+    ms = []
+    for i in range(3 + 2 * reps):
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        mine._minecapi.voxel_loss(pred.data_ptr(), ll_d.data_ptr(), mm_d.data_ptr(), shape, edge,
+                                  l0, l1, loss.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        ms.append(e0.elapsed_time(e1))
+    k_ms = float(np.median(ms[3:]))
+    out['voxel_loss_kernel'] = dict(ms=k_ms, bytes_per_voxel=10, gb_s=10 * n ** 3 / k_ms / 1e6,
+                                    timing='HIP events around one launch, median of %d' % (2 * reps))
+    print(json.dumps(out['voxel_loss_kernel']), flush=True)
+
+    # candidate tables: Volume2Planner construction, before the first batch can be drawn
+    im = u8
+    w_dev = loss
+    w_host = loss.cpu().numpy()
+    out['weights_positive_fraction'] = float((w_host > 0).mean())
+    tables = {}
+    for name, host_entry, dev_entry in (
+            ('unweighted', (im, ll, mm), (im, ll_d, mm_d)),
+            ('mined', (im, ll, mm, w_host), (im, ll_d, mm_d, w_dev))):
+        t0 = time.perf_counter()
+        ph = batchgen.Volume2Planner([host_entry], 24, 64, 0.5)
+        t_h = (time.perf_counter() - t0) * 1e3
+        t_d, pd = timed(lambda: batchgen.Volume2Planner([dev_entry], 24, 64, 0.5, tables='device',
+                                                        device=ctx.device), 3)
+        t_up, _ = timed(lambda: batchgen.Volume2Planner([host_entry], 24, 64, 0.5,
+                                                        tables='device', device=ctx.device), 3)
+        same = all(a.tobytes() == b.tobytes() for a, b in zip(ph._cols, pd._cols))
+        # the three launches alone, class by class
+        kern = {}
+        for cc in range(2):
+            ks = []
+            for _ in range(4):
+                e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                e0.record()
+                mine.candidates_device(ll_d, mm_d, (12, 12, 12), cc,
+                                       w_dev if name == 'mined' else None, download=False)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                ks.append(e0.elapsed_time(e1))
+            kern['class%d_count_scan_fill_ms' % cc] = float(np.median(ks[1:]))
+        tables[name] = dict(host_ms=t_h, device_resident_ms=t_d, device_upload_ms=t_up,
+                            host_over_device_resident=t_h / t_d, rows=[int(v) for v in ph._n],
+                            downloaded_bytes=int(sum(ph._n)) * (16 if name == 'mined' else 12),
+                            identical_tables=bool(same), **kern)
+        print(json.dumps({name: tables[name]}), flush=True)
+        del ph, pd
+    out['tables'] = tables
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--mine-size', type=int, default=520)
     ap.add_argument('--what', default='unet,train,v2o,pipeline')
     ap.add_argument('--unet-size', type=int, default=264)
     ap.add_argument('--roi-precision', default='auto')
@@ -328,6 +436,11 @@ def main():
             kernels={k: round(v['ms'] / steps, 3) for k, v in ctx.timing_get().items()})
         ctx.timing(False)
         print(json.dumps(res['unet_train_b64_24cubed_f32']), flush=True)
+
+    if 'mine' in what:
+        res['mine'] = mine_bench(ctx, torch, a.mine_size)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'mine.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
