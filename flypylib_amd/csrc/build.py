@@ -1,4 +1,4 @@
-"""Build libfplhip.so, libfplbatch.so and libfplmine.so for gfx950 (MI355X) with hipcc, in-tree.
+"""Build libfplhip.so, libfplbatch.so, libfplmine.so and libfpllabels.so for gfx950 (MI355X) with hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -13,7 +13,8 @@ libfplbatch.so (include/fplbatch.h, the device batch generators) is a library of
 its sources live in csrc/batchgen/, are compiled with the same flags and stamps, and its
 version script exports the fplb_* prefix only - libfplhip.so's export list stays the
 fpl_* names of include/fplhip.h.  libfplmine.so (include/fplmine.h, hard-example mining:
-csrc/mine/, prefix fplm_*) is built the same way.
+csrc/mine/, prefix fplm_*) and libfpllabels.so (include/fpllabels.h, the labels and mask
+of write_labels_mask: csrc/labels/, prefix fpll_*) are built the same way.
 """
 import argparse
 import hashlib
@@ -31,6 +32,8 @@ BATCH_DIR = os.path.join(HERE, 'batchgen')
 BATCH_LIB = os.path.join(LIB_DIR, 'libfplbatch.so')
 MINE_DIR = os.path.join(HERE, 'mine')
 MINE_LIB = os.path.join(LIB_DIR, 'libfplmine.so')
+LABELS_DIR = os.path.join(HERE, 'labels')
+LABELS_LIB = os.path.join(LIB_DIR, 'libfpllabels.so')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -150,6 +153,7 @@ def build(force=False, jobs=4, verbose=True):
                    force, jobs, verbose)
     build_batch(force, jobs, verbose)
     build_mine(force, jobs, verbose)
+    build_labels(force, jobs, verbose)
     return LIB
 
 
@@ -171,6 +175,16 @@ def build_mine(force=False, jobs=4, verbose=True):
             for f in sorted(os.listdir(MINE_DIR)) if f.endswith('.hip')]
     return _build_library(MINE_LIB, 'fplm_*', srcs, MINE_DIR,
                           _digest(_local_headers(MINE_DIR) + [os.path.join(inc, 'fplmine.h')]),
+                          force, jobs, verbose)
+
+
+def build_labels(force=False, jobs=4, verbose=True):
+    """libfpllabels.so from csrc/labels/*.hip, as build_batch; exports fpll_* only"""
+    inc = os.path.join(ROOT, 'include')
+    srcs = [(f, 'labels_' + f[:-4], ['-I' + inc])
+            for f in sorted(os.listdir(LABELS_DIR)) if f.endswith('.hip')]
+    return _build_library(LABELS_LIB, 'fpll_*', srcs, LABELS_DIR,
+                          _digest(_local_headers(LABELS_DIR) + [os.path.join(inc, 'fpllabels.h')]),
                           force, jobs, verbose)
 
 

@@ -82,13 +82,25 @@ def tbars_to_json_format_raveler(tbars_np, json_file=None):
     return _dump(doc, json_file)
 
 
-def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix):
+def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix, device=None):
     """training labels and mask around annotated T-bars (reference :251-310): label 1
     within `radius_use` of a T-bar; the mask is cleared in the shell between
     `radius_use` and `radius_ign` (neither positive nor negative) and within
     `buffer_size` of the faces.  Written as the reference's '<prefix>_labels.h5' /
     '<prefix>_mask.h5' (dataset 'main') and as '<prefix>_labels.npy' / '<prefix>_mask.npy',
-    and returned."""
+    and returned.
+
+    device=None (default) is the host path: numpy in, numpy out.  device=<int> or True (the
+    runtime's default device) renders both volumes with libfpllabels.so's kernel: `roi_mask`
+    is a numpy uint8 array (uploaded once) or a contiguous uint8 torch tensor on that device,
+    the result a pair of resident uint8 torch tensors that gen_volume2(device=...) and
+    FplNetwork.voxel_loss(device=...) take as they are; the files are written only when
+    `prefix` is not None.  A T-bar whose cube leaves the volume is a ValueError there
+    (labels.plan_tbars).  No host fallback: a missing library raises."""
+    if device is not None:
+        from . import labels as _labels
+        return _labels.write_labels_mask_device(tbars, roi_mask, radius_use, radius_ign,
+                                                buffer_size, prefix, device)
     radius_use_flt = fplutils.set_filter(radius_use)
     if radius_ign is not None:
         radius_ign_flt = 1 - fplutils.set_filter(radius_ign)

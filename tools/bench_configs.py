@@ -28,6 +28,11 @@
             (HIP events; GB/s at 10 B/voxel), and gen_volume2's candidate tables built by
             Volume2Planner on the host (nonzero) against tables='device' (libfplmine.so), for
             an unweighted and a mined (weighted) volume; written to profiles/mine.json
+  labels    fplsynapses.write_labels_mask on the host against device=..., in one process, at
+            520^3 and 256^3, one T-bar per 16^3 voxels (the density of tools/example_flow.py),
+            radii 3 / 6 and 6 / 12: the public call from a host roi_mask and from a resident
+            one, the planners (plan_tbars + plan_bricks) alone, the kernel alone (HIP events;
+            GB/s at 3 B/voxel) and the bytes uploaded; written to profiles/labels.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -251,6 +256,84 @@ def mine_bench(ctx, torch, n=520, reps=5):
     return out
 
 
+def labels_bench(ctx, torch, sizes=(520, 256), reps=5):
+    """write_labels_mask, host path against device path"""
+    from flypylib_amd import fplsynapses, labels
+    dev = torch.device('cuda', ctx.device)
+    rows = []
+    for n in sizes:
+        shape = (n,) * 3
+        for ru, ri in ((3, 6), (6, 12)):
+            half, step, buf = max(ru, ri), 16, 14
+            rs = np.random.RandomState(n + ru)
+            grid = np.arange(half + 3, n - half - 3, step)
+            locs = np.array([(x, y, z) for z in grid for y in grid for x in grid], np.float64)
+            locs += rs.randint(-3, 4, locs.shape)
+            rs.shuffle(locs)
+            tbars = {'locs': locs, 'conf': np.ones(len(locs))}
+            roi = np.ones(shape, np.uint8)
+            row = dict(volume=list(shape), voxels=n ** 3, radius_use=ru, radius_ign=ri,
+                       buffer_size=buf, tbars=len(locs), density='one T-bar per %d^3 voxels' % step)
+
+            t0 = time.perf_counter()
+            host = fplsynapses.write_labels_mask(tbars, roi, ru, ri, buf, None)
+            row['host_ms'] = (time.perf_counter() - t0) * 1e3
+
+            def timed(fn, k):
+                fn()
+                torch.cuda.synchronize(dev)
+                ts = []
+                for _ in range(k):
+                    t0 = time.perf_counter()
+                    r = fn()
+                    torch.cuda.synchronize(dev)
+                    ts.append(time.perf_counter() - t0)
+                return float(np.median(ts)) * 1e3, r
+
+            row['device_ms'], got = timed(lambda: fplsynapses.write_labels_mask(
+                tbars, roi, ru, ri, buf, None, device=ctx.device), reps)
+            roi_d = torch.from_numpy(roi).to(dev)
+            row['device_resident_roi_ms'], _ = timed(lambda: fplsynapses.write_labels_mask(
+                tbars, roi_d, ru, ri, buf, None, device=ctx.device), reps)
+            row['identical'] = bool(np.array_equal(got[0].cpu().numpy(), host[0])
+                                    and np.array_equal(got[1].cpu().numpy(), host[1]))
+            row['host_over_device'] = row['host_ms'] / row['device_ms']
+            del host
+
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                table = labels.plan_tbars(tbars, shape, ru, ri)
+                offsets, index = labels.plan_bricks(table, shape, half)
+                ts.append(time.perf_counter() - t0)
+            row['planner_ms'] = float(np.median(ts)) * 1e3
+            row['pairs'] = int(len(index))
+            row['longest_brick_list'] = int(np.diff(offsets).max())
+            row['upload_bytes_tables'] = int(table.nbytes + offsets.nbytes + index.nbytes)
+            row['upload_bytes_roi_from_host'] = int(roi.nbytes)
+
+            tabs = [torch.from_numpy(a).to(dev) for a in (table, offsets, index)]
+            ll, mm = (torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(2))
+            ms = []
+            for i in range(3 + 2 * reps):
+                e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                e0.record()
+                labels._labelscapi.labels_mask(
+                    roi_d.data_ptr(), tabs[0].data_ptr(), len(table), tabs[1].data_ptr(),
+                    tabs[2].data_ptr(), len(index), shape, ru, ri, buf, ll.data_ptr(),
+                    mm.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                ms.append(e0.elapsed_time(e1))
+            k_ms = float(np.median(ms[3:]))
+            row['kernel'] = dict(ms=k_ms, bytes_per_voxel=3, gb_s=3 * n ** 3 / k_ms / 1e6,
+                                 timing='HIP events around one launch, median of %d' % (2 * reps))
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del got, roi_d, ll, mm, tabs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
@@ -441,6 +524,11 @@ def main():
         res['mine'] = mine_bench(ctx, torch, a.mine_size)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'mine.json')
+
+    if 'labels' in what:
+        res['labels'] = labels_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'labels.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)

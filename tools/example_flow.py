@@ -45,6 +45,10 @@ def main(argv=None):
     ap.add_argument('--device-batches', action='store_true',
                     help='cut and augment the training batches on the GPU '
                          '(gen_volume2(device=True)): same batches, bit for bit')
+    ap.add_argument('--device-labels', action='store_true',
+                    help='render the training labels and mask on the GPU '
+                         '(write_labels_mask(device=True)) and feed the resident tensors to '
+                         'gen_volume2(device=True): same volumes and batches, bit for bit')
     a = ap.parse_args(argv)
     data_dir = a.out or tempfile.mkdtemp(prefix='fpl_example_')
     os.makedirs(data_dir, exist_ok=True)
@@ -55,8 +59,13 @@ def main(argv=None):
         im, tbars = make_region(seed, a.size, buffer_sz, radius['use'])
         np.save('%s/%d_im.npy' % (data_dir, prefix), im)
         fplsynapses.tbars_to_json_format_raveler(tbars, '%s/%d_synapses.json' % (data_dir, prefix))
-        fplsynapses.write_labels_mask(tbars, np.ones(im.shape, 'uint8'), radius['use'],
-                                      radius['ign'], buffer_sz, '%s/%d' % (data_dir, prefix))
+        on_device = a.device_labels and prefix == 0      # the training region; no files then
+        lm = fplsynapses.write_labels_mask(tbars, np.ones(im.shape, 'uint8'), radius['use'],
+                                           radius['ign'], buffer_sz,
+                                           None if on_device else '%s/%d' % (data_dir, prefix),
+                                           device=True if on_device else None)
+        if prefix == 0:
+            train_lm = lm
         evals[prefix] = [['%s/%d_im.npy' % (data_dir, prefix),
                           '%s/%d_synapses.json' % (data_dir, prefix)]]
 
@@ -64,9 +73,12 @@ def main(argv=None):
     network.infer_sz = (52, 52, 52)
     train_data = [['%s/0_im.npy' % data_dir, '%s/0_labels.npy' % data_dir,
                    '%s/0_mask.npy' % data_dir]]
+    if a.device_labels:          # labels and mask never leave the GPU
+        train_data = [('%s/0_im.npy' % data_dir,) + tuple(train_lm)]
     generator = fplobjdetect.gen_volume2(train_data, network.rf_size, a.batch, 0.5,
                                          rng=np.random.RandomState(0),
-                                         device=True if a.device_batches else None)
+                                         device=True if a.device_batches or a.device_labels
+                                         else None)
     network.train(generator, a.steps, a.epochs, '%s/log.csv' % data_dir, '%s/epoch' % data_dir)
     network.save_network('%s/net' % data_dir)
 
