@@ -3,12 +3,10 @@
 A missing library is an error (`FplBatchError`), never a silent host fallback.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, 'lib', 'libfplbatch.so')
+from ._sidelib import SideLibrary
 
 ABI_VERSION = 1
 U8, F32 = 0, 1
@@ -39,47 +37,20 @@ SIGNATURES = {
                               _vp, _vp, _vp]),
 }
 
-_lib = None
 
-
-def load_library(path=None):
-    """dlopen libfplbatch.so and bind every declared symbol (no GPU needed)"""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    if not os.path.exists(path):
-        raise FplBatchError(
-            'libfplbatch.so not found at %s - build it with `python -m flypylib_amd.csrc.build` '
-            '(device batch generators have no host fallback; use device=None for the host '
-            'generators)' % path)
-    # one HIP runtime per process, shared with torch and libfplhip.so: the same preload
-    # rule as _capi.load_library
-    if not os.environ.get('FPL_NO_TORCH_PRELOAD'):
-        try:
-            import torch  # noqa: F401
-        except Exception:       # noqa: BLE001
-            pass
-    lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fplb_abi_version() != ABI_VERSION:
-        raise FplBatchError('libfplbatch.so ABI %d, binding expects %d'
-                            % (lib.fplb_abi_version(), ABI_VERSION))
+def _check_structs(lib):
+    """struct fplb_volume / fplb_record are the library's size"""
     vb, rb = _i32(), _i32()
-    check(lib, lib.fplb_struct_sizes(C.byref(vb), C.byref(rb)))
+    _side.check(lib, lib.fplb_struct_sizes(C.byref(vb), C.byref(rb)))
     if (vb.value, rb.value) != (VOLUME.itemsize, RECORD.itemsize):
         raise FplBatchError('libfplbatch.so structs are %d / %d bytes, the binding\'s %d / %d'
                             % (vb.value, rb.value, VOLUME.itemsize, RECORD.itemsize))
-    _lib = lib
-    return lib
 
 
-def check(lib, rc):
-    if rc != 0:
-        raise FplBatchError((lib.fplb_last_error() or b'').decode() or 'rc %d' % rc)
+_side = SideLibrary('libfplbatch.so', 'fplb', FplBatchError, SIGNATURES, ABI_VERSION,
+                    'device batch generators have no host fallback; use device=None for the host '
+                    'generators', _check_structs)
+LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 
 
 def gather(vols_ptr, n_vols, recs_ptr, batch, context, src_dtype, noise, label_mode,

@@ -6,10 +6,8 @@ here takes raw device addresses and a raw hipStream_t; flypylib_amd/labels.py pu
 tensors around it.
 """
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, 'lib', 'libfpllabels.so')
+from ._sidelib import SideLibrary
 
 ABI_VERSION = 1
 BRICK = (4, 8, 128)          # FPLL_BRICK_Z, FPLL_BRICK_Y, FPLL_BRICK_X
@@ -32,42 +30,10 @@ SIGNATURES = {
                                    _vp, _vp]),
 }
 
-_lib = None
-
-
-def load_library(path=None):
-    """dlopen libfpllabels.so and bind every declared symbol (no GPU needed)"""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    if not os.path.exists(path):
-        raise FplLabelsError(
-            'libfpllabels.so not found at %s - build it with `python -m flypylib_amd.csrc.build` '
-            '(device write_labels_mask has no host fallback; use device=None for the host path)'
-            % path)
-    # one HIP runtime per process, shared with torch and libfplhip.so: the same preload
-    # rule as _capi.load_library
-    if not os.environ.get('FPL_NO_TORCH_PRELOAD'):
-        try:
-            import torch  # noqa: F401
-        except Exception:       # noqa: BLE001
-            pass
-    lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fpll_abi_version() != ABI_VERSION:
-        raise FplLabelsError('libfpllabels.so ABI %d, binding expects %d'
-                             % (lib.fpll_abi_version(), ABI_VERSION))
-    _lib = lib
-    return lib
-
-
-def check(lib, rc):
-    if rc != 0:
-        raise FplLabelsError((lib.fpll_last_error() or b'').decode() or 'rc %d' % rc)
+_side = SideLibrary('libfpllabels.so', 'fpll', FplLabelsError, SIGNATURES, ABI_VERSION,
+                    'device write_labels_mask has no host fallback; use device=None for the host '
+                    'path')
+LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 
 
 def labels_mask(roi_ptr, tbars_ptr, n_tbars, offsets_ptr, index_ptr, n_index, dims, radius_use,

@@ -6,10 +6,8 @@ here take raw device addresses and a raw hipStream_t; flypylib_amd/mine.py puts 
 around them.
 """
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, 'lib', 'libfplmine.so')
+from ._sidelib import SideLibrary
 
 ABI_VERSION = 1
 CHUNK = 4096                 # FPLM_CHUNK
@@ -35,41 +33,9 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp]),
 }
 
-_lib = None
-
-
-def load_library(path=None):
-    """dlopen libfplmine.so and bind every declared symbol (no GPU needed)"""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or LIB_PATH
-    if not os.path.exists(path):
-        raise FplMineError(
-            'libfplmine.so not found at %s - build it with `python -m flypylib_amd.csrc.build` '
-            '(device mining has no host fallback; use device=None for the host path)' % path)
-    # one HIP runtime per process, shared with torch and libfplhip.so: the same preload
-    # rule as _capi.load_library
-    if not os.environ.get('FPL_NO_TORCH_PRELOAD'):
-        try:
-            import torch  # noqa: F401
-        except Exception:       # noqa: BLE001
-            pass
-    lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fplm_abi_version() != ABI_VERSION:
-        raise FplMineError('libfplmine.so ABI %d, binding expects %d'
-                           % (lib.fplm_abi_version(), ABI_VERSION))
-    _lib = lib
-    return lib
-
-
-def check(lib, rc):
-    if rc != 0:
-        raise FplMineError((lib.fplm_last_error() or b'').decode() or 'rc %d' % rc)
+_side = SideLibrary('libfplmine.so', 'fplm', FplMineError, SIGNATURES, ABI_VERSION,
+                    'device mining has no host fallback; use device=None for the host path')
+LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 
 
 def scratch_bytes(n_voxels):

@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from . import _batchcapi, fplobjdetect, fplutils
+from . import _batchcapi, _device, fplobjdetect, fplutils
 
 RECORD = _batchcapi.RECORD
 _FLIP0, _FLIP1, _FLIP2 = (_batchcapi.FLIP_AXIS0, _batchcapi.FLIP_AXIS1,
@@ -234,7 +234,7 @@ class Volume2Planner(_Planner):
         for tr in train_data:
             if isinstance(tr[1], str) and not tr[1].endswith('.npy'):
                 tr = [tr[0], '%slabels.h5' % tr[1], '%smask.h5' % tr[1]] + list(tr[2:])
-            im, ll, mm, ww = (a if a is None or mine.is_device_tensor(a)
+            im, ll, mm, ww = (a if a is None or _device.is_device_tensor(a)
                               else fplobjdetect._load_main(a)
                               for a in (list(tr[:4]) + [None])[:4])
             vols.append((im, mine.to_device_u8(ll, dev), mine.to_device_u8(mm, dev),
@@ -384,21 +384,11 @@ class DeviceBatches:
         ring = int(ring)
         if ring < 2:
             raise ValueError('ring=%d: at least 2 buffer pairs' % ring)
-        try:
-            import torch
-        except Exception as e:      # noqa: BLE001
-            raise RuntimeError('device batches need torch (%s: %s); use device=None for the '
-                               'host generator %s' % (type(e).__name__, e, plan.host_name))
-        _batchcapi.load_library()                  # FplBatchError if it is not built
-        if device is True:
-            from . import runtime
-            device = runtime.default_device()
-        device = int(device)
-        if not torch.cuda.is_available() or device >= torch.cuda.device_count():
-            raise RuntimeError('device batches on cuda:%d: torch sees %d GPUs'
-                               % (device, torch.cuda.device_count() if torch.cuda.is_available() else 0))
-        self._torch, self.ring, self.device = torch, ring, device
-        self._dev = dev = torch.device('cuda', device)
+        torch = _device.require_torch('device batches need', 'use device=None for the host '
+                                      'generator %s' % plan.host_name)
+        # FplBatchError if the library is not built
+        self._dev = dev = _device.torch_device(device, 'device batches', _batchcapi.load_library)
+        self._torch, self.ring, self.device = torch, ring, dev.index
         self._src_dtype = src_dtype
         want = np.float32 if src_dtype == _batchcapi.F32 else np.uint8
         # what a planner left resident on this device is not uploaded a second time

@@ -18,39 +18,13 @@
 // the batches are bit-identical to the host generators'.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-#include <exception>
-
 #include "fplbatch.h"
+#include "../side/side_abi.h"
 
-#define FPLB_EXPORT extern "C" __attribute__((visibility("default")))
-#define FPLB_MAX_ERR 512
-
-static thread_local char g_fplb_err[FPLB_MAX_ERR] = {0};
-
-static int fplb_fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_fplb_err, sizeof(g_fplb_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-static int fplb_fail_exception(const char *fn) {
-  try {
-    throw;
-  } catch (const std::exception &e) {
-    return fplb_fail("%s: C++ exception: %s", fn, e.what());
-  } catch (...) {
-    return fplb_fail("%s: unknown C++ exception", fn);
-  }
-}
-
-// the guard of every entry point, written as a function-try-block:
-//   int fplb_x(...) try { ... } FPLB_CATCH()
-#define FPLB_CATCH()                                                           \
-  catch (...) { return fplb_fail_exception(__func__); }
+// this library's spelling of the shared shell
+#define FPLB_EXPORT SIDE_EXPORT
+#define FPLB_CATCH() SIDE_CATCH()
+#define fplb_fail side_fail
 
 namespace {
 
@@ -167,15 +141,13 @@ int launch(const fplb_volume *vols, int n_vols, const fplb_record *recs, int bat
   hipLaunchKernelGGL((gather_kernel<SrcT, NOISE>), grid, dim3(TILE * ROWS), 0, st, vols, n_vols,
                      recs, s0, s1, s2, tiles_k, tiles_j * tiles_k, src_dtype, label_mode, data,
                      labels);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fplb_fail("fplb_gather: launch failed: %s", hipGetErrorString(e));
-  return 0;
+  return launched("fplb_gather");
 }
 
 }  // namespace
 
 FPLB_EXPORT const char *fplb_last_error(void) try {
-  return g_fplb_err;
+  return side_err;
 } catch (...) { return "fplb_last_error: C++ exception"; }
 
 FPLB_EXPORT int fplb_abi_version(void) try {

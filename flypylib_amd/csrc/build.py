@@ -1,4 +1,4 @@
-"""Build libfplhip.so, libfplbatch.so, libfplmine.so and libfpllabels.so for gfx950 (MI355X) with hipcc, in-tree.
+"""Build libfplhip.so and the side libraries for gfx950 (MI355X) with hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -9,12 +9,11 @@ to it - modification times say nothing on a tree that ships objects, and the dri
 build check must compile what it ships.  hipcc cross-compiles without a GPU, so this
 runs in the CPU-only build container.
 
-libfplbatch.so (include/fplbatch.h, the device batch generators) is a library of its own:
-its sources live in csrc/batchgen/, are compiled with the same flags and stamps, and its
-version script exports the fplb_* prefix only - libfplhip.so's export list stays the
-fpl_* names of include/fplhip.h.  libfplmine.so (include/fplmine.h, hard-example mining:
-csrc/mine/, prefix fplm_*) and libfpllabels.so (include/fpllabels.h, the labels and mask
-of write_labels_mask: csrc/labels/, prefix fpll_*) are built the same way.
+Every row of SIDE_LIBRARIES is a library of its own: its sources live in a directory under
+csrc/, are compiled with the same flags and stamps, and its version script exports its own
+prefix only - libfplhip.so's export list stays the fpl_* names of include/fplhip.h.  The
+side libraries share the C shell of csrc/side/side_abi.h, which is part of their stamps and
+not of libfplhip.so's.
 """
 import argparse
 import hashlib
@@ -28,12 +27,14 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 OBJ_DIR = os.path.join(HERE, 'build')
 LIB_DIR = os.path.join(os.path.dirname(HERE), 'lib')
 LIB = os.path.join(LIB_DIR, 'libfplhip.so')
-BATCH_DIR = os.path.join(HERE, 'batchgen')
-BATCH_LIB = os.path.join(LIB_DIR, 'libfplbatch.so')
-MINE_DIR = os.path.join(HERE, 'mine')
-MINE_LIB = os.path.join(LIB_DIR, 'libfplmine.so')
-LABELS_DIR = os.path.join(HERE, 'labels')
-LABELS_LIB = os.path.join(LIB_DIR, 'libfpllabels.so')
+# key (its binding is flypylib_amd/_<key>capi.py), source directory under csrc/ (and the
+# stem of its objects), export prefix, public header under include/, library under lib/
+SIDE_LIBRARIES = (
+    ('batch', 'batchgen', 'fplb', 'fplbatch.h', 'libfplbatch.so'),     # device batch generators
+    ('mine', 'mine', 'fplm', 'fplmine.h', 'libfplmine.so'),            # hard-example mining
+    ('labels', 'labels', 'fpll', 'fpllabels.h', 'libfpllabels.so'),    # write_labels_mask
+)
+SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -151,40 +152,20 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    build_batch(force, jobs, verbose)
-    build_mine(force, jobs, verbose)
-    build_labels(force, jobs, verbose)
+    for row in SIDE_LIBRARIES:
+        build_side(row[0], force, jobs, verbose)
     return LIB
 
 
-def build_batch(force=False, jobs=4, verbose=True):
-    """libfplbatch.so from csrc/batchgen/*.hip: same flags, same SHA-stamped rebuild, a
-    version script that exports fplb_* only"""
-    inc = os.path.join(ROOT, 'include')
-    srcs = [(f, 'batchgen_' + f[:-4], ['-I' + inc])
-            for f in sorted(os.listdir(BATCH_DIR)) if f.endswith('.hip')]
-    return _build_library(BATCH_LIB, 'fplb_*', srcs, BATCH_DIR,
-                          _digest(_local_headers(BATCH_DIR) + [os.path.join(inc, 'fplbatch.h')]),
-                          force, jobs, verbose)
-
-
-def build_mine(force=False, jobs=4, verbose=True):
-    """libfplmine.so from csrc/mine/*.hip, as build_batch; exports fplm_* only"""
-    inc = os.path.join(ROOT, 'include')
-    srcs = [(f, 'mine_' + f[:-4], ['-I' + inc])
-            for f in sorted(os.listdir(MINE_DIR)) if f.endswith('.hip')]
-    return _build_library(MINE_LIB, 'fplm_*', srcs, MINE_DIR,
-                          _digest(_local_headers(MINE_DIR) + [os.path.join(inc, 'fplmine.h')]),
-                          force, jobs, verbose)
-
-
-def build_labels(force=False, jobs=4, verbose=True):
-    """libfpllabels.so from csrc/labels/*.hip, as build_batch; exports fpll_* only"""
-    inc = os.path.join(ROOT, 'include')
-    srcs = [(f, 'labels_' + f[:-4], ['-I' + inc])
-            for f in sorted(os.listdir(LABELS_DIR)) if f.endswith('.hip')]
-    return _build_library(LABELS_LIB, 'fpll_*', srcs, LABELS_DIR,
-                          _digest(_local_headers(LABELS_DIR) + [os.path.join(inc, 'fpllabels.h')]),
+def build_side(key, force=False, jobs=4, verbose=True):
+    """one row of SIDE_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that
+    exports the row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES if r[0] == key)
+    src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
+    srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
+            for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]
+    return _build_library(os.path.join(LIB_DIR, lib), prefix + '_*', srcs, src_dir,
+                          _digest(_local_headers(src_dir) + [SIDE_ABI, os.path.join(inc, header)]),
                           force, jobs, verbose)
 
 

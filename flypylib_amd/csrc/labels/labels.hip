@@ -20,39 +20,13 @@
 // start at an odd byte, the end of a row).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-#include <exception>
-
 #include "fpllabels.h"
+#include "../side/side_abi.h"
 
-#define FPLL_EXPORT extern "C" __attribute__((visibility("default")))
-#define FPLL_MAX_ERR 512
-
-static thread_local char g_fpll_err[FPLL_MAX_ERR] = {0};
-
-static int fpll_fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_fpll_err, sizeof(g_fpll_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-static int fpll_fail_exception(const char *fn) {
-  try {
-    throw;
-  } catch (const std::exception &e) {
-    return fpll_fail("%s: C++ exception: %s", fn, e.what());
-  } catch (...) {
-    return fpll_fail("%s: unknown C++ exception", fn);
-  }
-}
-
-// the guard of every entry point, written as a function-try-block:
-//   int fpll_x(...) try { ... } FPLL_CATCH()
-#define FPLL_CATCH()                                                           \
-  catch (...) { return fpll_fail_exception(__func__); }
+// this library's spelling of the shared shell
+#define FPLL_EXPORT SIDE_EXPORT
+#define FPLL_CATCH() SIDE_CATCH()
+#define fpll_fail side_fail
 
 namespace {
 
@@ -202,18 +176,10 @@ __global__ __launch_bounds__(BLOCK) void labels_mask_kernel(
   }
 }
 
-bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-int launched(const char *fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fpll_fail("%s: launch failed: %s", fn, hipGetErrorString(e));
-  return 0;
-}
-
 }  // namespace
 
 FPLL_EXPORT const char *fpll_last_error(void) try {
-  return g_fpll_err;
+  return side_err;
 } catch (...) { return "fpll_last_error: C++ exception"; }
 
 FPLL_EXPORT int fpll_abi_version(void) try {
@@ -231,11 +197,8 @@ FPLL_EXPORT int fpll_labels_mask(const uint8_t *roi, const int32_t *tbars, int64
     if (dims[a] < 1) return fpll_fail("%s: dims (%lld,%lld,%lld) must be positive", fn,
                                       (long long)dims[0], (long long)dims[1], (long long)dims[2]);
   const int64_t lim = 2147483647;
-  if (dims[0] > lim || dims[1] > lim || dims[2] > lim || dims[1] * dims[2] > lim ||
-      dims[0] * (dims[1] * dims[2]) > lim)
-    return fpll_fail("%s: a volume of (%lld,%lld,%lld) voxels exceeds the 2^31 - 1 voxels the "
-                     "brick tables can index; render it in parts", fn, (long long)dims[0],
-                     (long long)dims[1], (long long)dims[2]);
+  int64_t voxels;
+  if (volume_voxels(fn, dims, "the brick tables", "render it in parts", &voxels)) return 1;
   if (radius_use < 0 || radius_ign < 0 || radius_use > FPLL_MAX_RADIUS ||
       radius_ign > FPLL_MAX_RADIUS)
     return fpll_fail("%s: radius_use %d / radius_ign %d must lie in [0, %d]", fn, radius_use,
@@ -248,7 +211,7 @@ FPLL_EXPORT int fpll_labels_mask(const uint8_t *roi, const int32_t *tbars, int64
                      (long long)n_index);
   if (!aligned(tbars, 4) || !aligned(brick_offsets, 4) || !aligned(brick_index, 4))
     return fpll_fail("%s: a table is not aligned to an int32", fn);
-  const size_t n = (size_t)(dims[0] * dims[1] * dims[2]);
+  const size_t n = (size_t)voxels;
   if (roi == labels || roi == mask || labels == mask ||
       (labels < mask ? labels + n > mask : mask + n > labels))
     return fpll_fail("%s: roi, labels and mask must be distinct buffers", fn);

@@ -28,39 +28,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <exception>
 
 #include "fplmine.h"
+#include "../side/side_abi.h"
 
-#define FPLM_EXPORT extern "C" __attribute__((visibility("default")))
-#define FPLM_MAX_ERR 512
-
-static thread_local char g_fplm_err[FPLM_MAX_ERR] = {0};
-
-static int fplm_fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_fplm_err, sizeof(g_fplm_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-static int fplm_fail_exception(const char *fn) {
-  try {
-    throw;
-  } catch (const std::exception &e) {
-    return fplm_fail("%s: C++ exception: %s", fn, e.what());
-  } catch (...) {
-    return fplm_fail("%s: unknown C++ exception", fn);
-  }
-}
-
-// the guard of every entry point, written as a function-try-block:
-//   int fplm_x(...) try { ... } FPLM_CATCH()
-#define FPLM_CATCH()                                                           \
-  catch (...) { return fplm_fail_exception(__func__); }
+// this library's spelling of the shared shell
+#define FPLM_EXPORT SIDE_EXPORT
+#define FPLM_CATCH() SIDE_CATCH()
+#define fplm_fail side_fail
 
 namespace {
 
@@ -287,8 +262,6 @@ __global__ __launch_bounds__(BLOCK) void fill_kernel(Candidates c, Geometry g, u
   }
 }
 
-bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // dims and border -> Geometry; a message names what is refused
 int geometry(const char *fn, const int64_t dims[3], const int32_t border[3], const char *border_name,
              Geometry *g) {
@@ -298,13 +271,9 @@ int geometry(const char *fn, const int64_t dims[3], const int32_t border[3], con
     if (border[a] < 0) return fplm_fail("%s: %s (%d,%d,%d) must not be negative", fn, border_name,
                                         border[0], border[1], border[2]);
   }
-  const int64_t lim = 2147483647;
-  if (dims[0] > lim || dims[1] > lim || dims[2] > lim || dims[1] * dims[2] > lim ||
-      dims[0] * (dims[1] * dims[2]) > lim)
-    return fplm_fail("%s: a volume of (%lld,%lld,%lld) voxels exceeds the 2^31 - 1 voxels int32 "
-                     "rows and counts can index; mine it in parts", fn, (long long)dims[0],
-                     (long long)dims[1], (long long)dims[2]);
-  g->n = (uint32_t)(dims[0] * dims[1] * dims[2]);
+  int64_t n;
+  if (volume_voxels(fn, dims, "int32 rows and counts", "mine it in parts", &n)) return 1;
+  g->n = (uint32_t)n;
   g->d0 = (int)dims[0];
   g->d1 = (uint32_t)dims[1];
   g->d2 = (uint32_t)dims[2];
@@ -312,12 +281,6 @@ int geometry(const char *fn, const int64_t dims[3], const int32_t border[3], con
   g->b0 = border[0] > g->d0 ? g->d0 : border[0];
   g->b1 = border[1] > (int)g->d1 ? (int)g->d1 : border[1];
   g->b2 = border[2] > (int)g->d2 ? (int)g->d2 : border[2];
-  return 0;
-}
-
-int launched(const char *fn) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fplm_fail("%s: launch failed: %s", fn, hipGetErrorString(e));
   return 0;
 }
 
@@ -346,7 +309,7 @@ int candidate_args(const char *fn, const uint8_t *labels, const uint8_t *mask, c
 }  // namespace
 
 FPLM_EXPORT const char *fplm_last_error(void) try {
-  return g_fplm_err;
+  return side_err;
 } catch (...) { return "fplm_last_error: C++ exception"; }
 
 FPLM_EXPORT int fplm_abi_version(void) try {

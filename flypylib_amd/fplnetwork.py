@@ -297,13 +297,13 @@ class FplNetwork:
 
     def _voxel_loss_device(self, image, lm_prefix, l0_thresh, l1_thresh, normalize, device):
         import torch
-        from . import mine
+        from . import _device, mine
         from .fplobjdetect import _load_main
         dev = mine.torch_device(device)
         if isinstance(lm_prefix, str):
             labels, mask = (_load_main('%s%s.h5' % (lm_prefix, n)) for n in ('labels', 'mask'))
         else:
-            labels, mask = (a if mine.is_device_tensor(a) else _load_main(a) for a in lm_prefix)
+            labels, mask = (a if _device.is_device_tensor(a) else _load_main(a) for a in lm_prefix)
         edge = [int(round(cc / 2)) for cc in self.rf_size]
         if min(edge) < 1:
             raise ValueError('rf_size %r: the device voxel_loss needs a border of at least one '

@@ -20,7 +20,7 @@ cube around it.  Per voxel v that is a rule without an order of execution:
 """
 import numpy as np
 
-from . import _labelscapi
+from . import _device, _labelscapi
 
 MAX_VOXELS = _labelscapi.MAX_VOXELS
 BRICK = _labelscapi.BRICK
@@ -158,31 +158,19 @@ def plan_bricks(locs, shape, half, brick=BRICK):
 
 # ---- device path ---------------------------------------------------------------------------
 
+is_device_tensor = _device.is_device_tensor
+
+
 def _torch():
-    try:
-        import torch
-    except Exception as e:      # noqa: BLE001
-        raise RuntimeError('device write_labels_mask needs torch (%s: %s); use device=None for '
-                           'the host path' % (type(e).__name__, e))
-    return torch
-
-
-def is_device_tensor(a):
-    return hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr') and bool(a.is_cuda)
+    return _device.require_torch('device write_labels_mask needs',
+                                 'use device=None for the host path')
 
 
 def torch_device(device):
-    """torch.device of `device` (an int, or True for the runtime's default device)"""
-    torch = _torch()
-    _labelscapi.load_library()                     # FplLabelsError if it is not built
-    if device is True:
-        from . import runtime
-        device = runtime.default_device()
-    device = int(device)
-    if not torch.cuda.is_available() or device >= torch.cuda.device_count():
-        raise RuntimeError('device write_labels_mask on cuda:%d: torch sees %d GPUs'
-                           % (device, torch.cuda.device_count() if torch.cuda.is_available() else 0))
-    return torch.device('cuda', device)
+    """torch.device of `device` (an int, or True for the runtime's default device);
+    FplLabelsError if the library is not built"""
+    _torch()
+    return _device.torch_device(device, 'device write_labels_mask', _labelscapi.load_library)
 
 
 def check_shape(shape):

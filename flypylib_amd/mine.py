@@ -8,7 +8,7 @@ call.  Nothing here falls back to the host when the library, torch or the GPU is
 """
 import numpy as np
 
-from . import _minecapi
+from . import _device, _minecapi
 
 MAX_VOXELS = _minecapi.MAX_VOXELS
 
@@ -69,31 +69,18 @@ def candidates_numpy(labels, mask, half, cc, weights=None):
 
 # ---- device path ---------------------------------------------------------------------------
 
+is_device_tensor = _device.is_device_tensor
+
+
 def _torch():
-    try:
-        import torch
-    except Exception as e:      # noqa: BLE001
-        raise RuntimeError('device mining needs torch (%s: %s); use device=None for the host '
-                           'path' % (type(e).__name__, e))
-    return torch
-
-
-def is_device_tensor(a):
-    return hasattr(a, 'is_cuda') and hasattr(a, 'data_ptr') and bool(a.is_cuda)
+    return _device.require_torch('device mining needs', 'use device=None for the host path')
 
 
 def torch_device(device):
-    """torch.device of `device` (an int, or True for the runtime's default device)"""
-    torch = _torch()
-    _minecapi.load_library()                       # FplMineError if it is not built
-    if device is True:
-        from . import runtime
-        device = runtime.default_device()
-    device = int(device)
-    if not torch.cuda.is_available() or device >= torch.cuda.device_count():
-        raise RuntimeError('device mining on cuda:%d: torch sees %d GPUs'
-                           % (device, torch.cuda.device_count() if torch.cuda.is_available() else 0))
-    return torch.device('cuda', device)
+    """torch.device of `device` (an int, or True for the runtime's default device);
+    FplMineError if the library is not built"""
+    _torch()
+    return _device.torch_device(device, 'device mining', _minecapi.load_library)
 
 
 def classes_u8(a):

@@ -4,14 +4,12 @@ the oracle (pinned to the reference by tests/golden/training_generators.npz)."""
 import hashlib
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from flypylib_amd import _batchcapi, batchgen, fplobjdetect
-from tests import batchgen_cases as cases
+from tests import batchgen_cases as cases, side_abi_cases as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -85,60 +83,13 @@ def test_records_are_the_c_struct():
         _batchcapi.gather(0, 1, 0, 1, (8, 8, 8), _batchcapi.F32, False, 0, 0, 0, 0)
 
 
-def _closing_brace(s, i):
-    assert s[i] == '{'
-    depth = 0
-    while True:
-        depth += {'{': 1, '}': -1}.get(s[i], 0)
-        if depth == 0:
-            return i
-        i += 1
-
-
-def _declared():
-    hdr = open(os.path.join(ROOT, 'include', 'fplbatch.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    return set(re.findall(r'\b(fplb_[a-z0-9_]+)\s*\(', hdr))
-
-
 def test_libfplbatch_exports_exactly_the_declared_names():
-    declared = _declared()
-    assert declared == set(_batchcapi.SIGNATURES) and len(declared) == 4
+    declared = abi.check_exports(_batchcapi, 'fplbatch.h', 'fplb', 4)
     assert not any(n.startswith('fpl_') for n in declared)
-    if shutil.which('nm') is None:
-        pytest.skip('nm is not installed')
-    out = subprocess.run(['nm', '-D', '--defined-only', _batchcapi.LIB_PATH],
-                         stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-    assert exported == declared, exported ^ declared
 
 
 def test_every_fplb_entry_point_is_guarded():
-    """every entry point is a function-try-block; the int ones end in FPLB_CATCH, which
-    turns the exception into an rc; no threads"""
-    csrc = os.path.join(ROOT, 'flypylib_amd', 'csrc', 'batchgen')
-    srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
-            if f.endswith(('.hip', '.h'))}
-    guarded = 0
-    for name in sorted(_declared()):
-        defs = [(f, m) for f, s in srcs.items() if f.endswith('.hip')
-                for m in re.finditer(r'^FPLB_EXPORT (?:int|const char \*)\s*' + name + r'\(', s, re.M)]
-        assert len(defs) == 1, (name, [f for f, _ in defs])
-        f, m = defs[0]
-        s = srcs[f]
-        i, depth = m.end() - 1, 0
-        while True:
-            depth += {'(': 1, ')': -1}.get(s[i], 0)
-            if depth == 0:
-                break
-            i += 1
-        assert s.startswith(') try {', i), '%s is not a function-try-block' % name
-        end = _closing_brace(s, i + len(') try '))
-        handler = ' catch (...) {' if name == 'fplb_last_error' else ' FPLB_CATCH()'
-        assert s.startswith(handler, end + 1), '%s: no handler after its body' % name
-        guarded += 1
-    assert guarded == 4
-    assert not any('std::thread' in s for s in srcs.values())
+    abi.check_guarded('batchgen', 'fplbatch.h', 'fplb', 4)
 
 
 def test_device_mode_refuses_what_it_does_not_take():

@@ -3,14 +3,12 @@ flypylib_amd/labels.py against the unchanged fplsynapses.write_labels_mask it sp
 planners of the device path, and the C ABI of libfpllabels.so."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from flypylib_amd import _labelscapi, fplsynapses, labels
-from tests import labels_cases as cases
+from tests import labels_cases as cases, side_abi_cases as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'synapses.npz'))
@@ -158,21 +156,8 @@ def test_plan_bricks_lists_every_pair_whose_cube_meets_the_brick(shape, half, br
 
 # ---- the C ABI of libfpllabels.so ---------------------------------------------------------------
 
-def _declared():
-    hdr = open(os.path.join(ROOT, 'include', 'fpllabels.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    return set(re.findall(r'\b(fpll_[a-z0-9_]+)\s*\(', hdr))
-
-
 def test_libfpllabels_exports_exactly_the_declared_names():
-    declared = _declared()
-    assert declared == set(_labelscapi.SIGNATURES) and len(declared) == N_EXPORTS
-    if shutil.which('nm') is None:
-        pytest.skip('nm is not installed')
-    out = subprocess.run(['nm', '-D', '--defined-only', _labelscapi.LIB_PATH],
-                         stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-    assert exported == declared, exported ^ declared
+    abi.check_exports(_labelscapi, 'fpllabels.h', 'fpll', N_EXPORTS)
 
 
 def test_the_other_libraries_keep_their_export_lists():
@@ -186,37 +171,8 @@ def test_the_other_libraries_keep_their_export_lists():
                 assert 'fpll_' not in open(os.path.join(d, f)).read(), f
 
 
-def _closing(s, i, open_, close):
-    assert s[i] == open_
-    depth = 0
-    while True:
-        depth += {open_: 1, close: -1}.get(s[i], 0)
-        if depth == 0:
-            return i
-        i += 1
-
-
 def test_every_fpll_entry_point_is_guarded():
-    """every entry point is a function-try-block; the int ones end in FPLL_CATCH, which turns
-    the exception into an rc; no threads"""
-    csrc = os.path.join(ROOT, 'flypylib_amd', 'csrc', 'labels')
-    srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
-            if f.endswith(('.hip', '.h'))}
-    guarded = 0
-    for name in sorted(_declared()):
-        defs = [(f, m) for f, s in srcs.items() if f.endswith('.hip')
-                for m in re.finditer(r'^FPLL_EXPORT (?:int|const char \*)\s*' + name + r'\(', s, re.M)]
-        assert len(defs) == 1, (name, [f for f, _ in defs])
-        f, m = defs[0]
-        s = srcs[f]
-        i = _closing(s, m.end() - 1, '(', ')')
-        assert s.startswith(') try {', i), '%s is not a function-try-block' % name
-        end = _closing(s, i + len(') try '), '{', '}')
-        handler = ' catch (...) {' if name == 'fpll_last_error' else ' FPLL_CATCH()'
-        assert s.startswith(handler, end + 1), '%s: no handler after its body' % name
-        guarded += 1
-    assert guarded == N_EXPORTS
-    assert not any('std::thread' in s for s in srcs.values())
+    abi.check_guarded('labels', 'fpllabels.h', 'fpll', N_EXPORTS)
 
 
 def test_refused_calls_leave_a_message_and_touch_no_gpu():

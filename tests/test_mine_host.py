@@ -3,36 +3,21 @@ executors of flypylib_amd/mine.py against the code they specify - FplNetwork.vox
 the nonzero()-built candidate tables of gen_volume2."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from flypylib_amd import FplNetwork, _minecapi, batchgen, fplobjdetect, mine
-from tests import batchgen_cases as cases
+from tests import batchgen_cases as cases, side_abi_cases as abi
 from tests.mine_cases import mining_case as _mining_case, ulp_distance as _ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_EXPORTS = 5
 
 
-def _declared():
-    hdr = open(os.path.join(ROOT, 'include', 'fplmine.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    return set(re.findall(r'\b(fplm_[a-z0-9_]+)\s*\(', hdr))
-
-
 def test_libfplmine_exports_exactly_the_declared_names():
-    declared = _declared()
-    assert declared == set(_minecapi.SIGNATURES) and len(declared) == N_EXPORTS
+    declared = abi.check_exports(_minecapi, 'fplmine.h', 'fplm', N_EXPORTS)
     assert not any(n.startswith(('fpl_', 'fplb_')) for n in declared)
-    if shutil.which('nm') is None:
-        pytest.skip('nm is not installed')
-    out = subprocess.run(['nm', '-D', '--defined-only', _minecapi.LIB_PATH],
-                         stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-    assert exported == declared, exported ^ declared
 
 
 def test_the_other_libraries_keep_their_export_lists():
@@ -45,37 +30,8 @@ def test_the_other_libraries_keep_their_export_lists():
             assert 'fplm_' not in open(os.path.join(csrc, f)).read(), f
 
 
-def _closing(s, i, open_, close):
-    assert s[i] == open_
-    depth = 0
-    while True:
-        depth += {open_: 1, close: -1}.get(s[i], 0)
-        if depth == 0:
-            return i
-        i += 1
-
-
 def test_every_fplm_entry_point_is_guarded():
-    """every entry point is a function-try-block; the int ones end in FPLM_CATCH, which turns
-    the exception into an rc; no threads"""
-    csrc = os.path.join(ROOT, 'flypylib_amd', 'csrc', 'mine')
-    srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
-            if f.endswith(('.hip', '.h'))}
-    guarded = 0
-    for name in sorted(_declared()):
-        defs = [(f, m) for f, s in srcs.items() if f.endswith('.hip')
-                for m in re.finditer(r'^FPLM_EXPORT (?:int|const char \*)\s*' + name + r'\(', s, re.M)]
-        assert len(defs) == 1, (name, [f for f, _ in defs])
-        f, m = defs[0]
-        s = srcs[f]
-        i = _closing(s, m.end() - 1, '(', ')')
-        assert s.startswith(') try {', i), '%s is not a function-try-block' % name
-        end = _closing(s, i + len(') try '), '{', '}')
-        handler = ' catch (...) {' if name == 'fplm_last_error' else ' FPLM_CATCH()'
-        assert s.startswith(handler, end + 1), '%s: no handler after its body' % name
-        guarded += 1
-    assert guarded == N_EXPORTS
-    assert not any('std::thread' in s for s in srcs.values())
+    abi.check_guarded('mine', 'fplmine.h', 'fplm', N_EXPORTS)
 
 
 def test_refused_calls_leave_a_message_and_touch_no_gpu():
