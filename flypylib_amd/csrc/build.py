@@ -1,4 +1,5 @@
-"""Build libfplhip.so and the side libraries for gfx950 (MI355X) with hipcc, in-tree.
+"""Build libfplhip.so, the side libraries and the stage libraries for gfx950 (MI355X) with
+hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -14,6 +15,11 @@ csrc/, are compiled with the same flags and stamps, and its version script expor
 prefix only - libfplhip.so's export list stays the fpl_* names of include/fplhip.h.  The
 side libraries share the C shell of csrc/side/side_abi.h, which is part of their stamps and
 not of libfplhip.so's.
+
+STAGE_LIBRARIES holds rows of the same shape, built in the same way: libraries that serve a
+stage of a side library rather than a device stage of their own (libfplplan.so plans the
+table libfpllabels.so's kernel reads).  They are a table of their own because SIDE_LIBRARIES
+is also the list of bindings _sidelib.bindings() / load_all() answer for, which stays as it is.
 """
 import argparse
 import hashlib
@@ -33,6 +39,9 @@ SIDE_LIBRARIES = (
     ('batch', 'batchgen', 'fplb', 'fplbatch.h', 'libfplbatch.so'),     # device batch generators
     ('mine', 'mine', 'fplm', 'fplmine.h', 'libfplmine.so'),            # hard-example mining
     ('labels', 'labels', 'fpll', 'fpllabels.h', 'libfpllabels.so'),    # write_labels_mask
+)
+STAGE_LIBRARIES = (
+    ('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),            # plan_bricks on the device
 )
 SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
@@ -152,15 +161,15 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in SIDE_LIBRARIES:
+    for row in SIDE_LIBRARIES + STAGE_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that
-    exports the row's prefix only"""
-    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES if r[0] == key)
+    """one row of SIDE_LIBRARIES or STAGE_LIBRARIES: same flags, same SHA-stamped rebuild, a
+    version script that exports the row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES + STAGE_LIBRARIES if r[0] == key)
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]

@@ -82,7 +82,8 @@ def tbars_to_json_format_raveler(tbars_np, json_file=None):
     return _dump(doc, json_file)
 
 
-def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix, device=None):
+def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix, device=None,
+                      planner='host'):
     """training labels and mask around annotated T-bars (reference :251-310): label 1
     within `radius_use` of a T-bar; the mask is cleared in the shell between
     `radius_use` and `radius_ign` (neither positive nor negative) and within
@@ -96,11 +97,17 @@ def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, pref
     the result a pair of resident uint8 torch tensors that gen_volume2(device=...) and
     FplNetwork.voxel_loss(device=...) take as they are; the files are written only when
     `prefix` is not None.  A T-bar whose cube leaves the volume is a ValueError there
-    (labels.plan_tbars).  No host fallback: a missing library raises."""
+    (labels.plan_tbars).  No host fallback: a missing library raises.
+
+    planner='host' (default) builds the kernel's brick table with numpy (labels.plan_bricks)
+    and uploads it; planner='device' uploads the T-bar table alone and builds the brick table
+    with libfplplan.so on the kernel's stream: the same bytes.  Any other value, and
+    planner='device' with device=None (the host loop plans nothing), is a ValueError."""
+    from . import labels as _labels
+    _labels.check_planner(planner, device)
     if device is not None:
-        from . import labels as _labels
         return _labels.write_labels_mask_device(tbars, roi_mask, radius_use, radius_ign,
-                                                buffer_size, prefix, device)
+                                                buffer_size, prefix, device, planner=planner)
     radius_use_flt = fplutils.set_filter(radius_use)
     if radius_ign is not None:
         radius_ign_flt = 1 - fplutils.set_filter(radius_ign)

@@ -1,7 +1,7 @@
 """Training labels and mask around annotated T-bars: the per-voxel rule of
 fplsynapses.write_labels_mask as a numpy executor (the specification; the CPU tests' and the
 GPU tests' oracle), the planners of the device path, and the device path itself over
-libfpllabels.so (include/fpllabels.h).
+libfpllabels.so (include/fpllabels.h) and - planner='device' - libfplplan.so (include/fplplan.h).
 
 `fplsynapses.write_labels_mask(device=...)` is the public surface; this module is what it
 calls.  Nothing here falls back to the host when the library, torch or the GPU is missing.
@@ -20,8 +20,9 @@ cube around it.  Per voxel v that is a rule without an order of execution:
 """
 import numpy as np
 
-from . import _device, _labelscapi
+from . import _device, _labelscapi, _plancapi
 
+PLANNERS = ('host', 'device')
 MAX_VOXELS = _labelscapi.MAX_VOXELS
 BRICK = _labelscapi.BRICK
 
@@ -124,11 +125,9 @@ def brick_counts(shape, brick=BRICK):
     return tuple((int(d) + b - 1) // b for d, b in zip(shape, brick))
 
 
-def plan_bricks(locs, shape, half, brick=BRICK):
-    """CSR table of the T-bars each brick has to look at: (offsets int32 (bricks + 1,),
-    index int32), bricks in C order of (brick z, brick y, brick x).  Brick b's list is
-    index[offsets[b]:offsets[b + 1]]: every T-bar of `locs` ((N, 3) of (x, y, z), inside the
-    volume with its cube) whose cube of half-width `half` meets the brick, in ascending j."""
+def _brick_ranges(locs, shape, half, brick):
+    """per T-bar the first brick `lo` and the brick counts `cnt` of its clamped range on
+    (z, y, x), their products `per` and the pair total"""
     nb = brick_counts(shape, brick)
     n_bricks = nb[0] * nb[1] * nb[2]
     if n_bricks + 1 > MAX_VOXELS:
@@ -145,7 +144,23 @@ def plan_bricks(locs, shape, half, brick=BRICK):
     if total > MAX_VOXELS:
         raise ValueError('%d (T-bar, brick) pairs exceed the int32 brick tables; render the '
                          'volume in parts' % total)
-    j = np.repeat(np.arange(len(locs), dtype=np.int64), per)
+    return nb, n_bricks, len(locs), lo, cnt, per, total
+
+
+def plan_pairs(locs, shape, half, brick=BRICK):
+    """the (T-bar, brick) pairs plan_bricks lists, len(plan_bricks(...)[1]), without building
+    the table: O(N).  The device planner is told this total; plan_bricks's own ValueError
+    beyond 2^31 - 1 pairs."""
+    return _brick_ranges(locs, shape, half, brick)[-1]
+
+
+def plan_bricks(locs, shape, half, brick=BRICK):
+    """CSR table of the T-bars each brick has to look at: (offsets int32 (bricks + 1,),
+    index int32), bricks in C order of (brick z, brick y, brick x).  Brick b's list is
+    index[offsets[b]:offsets[b + 1]]: every T-bar of `locs` ((N, 3) of (x, y, z), inside the
+    volume with its cube) whose cube of half-width `half` meets the brick, in ascending j."""
+    nb, n_bricks, n, lo, cnt, per, total = _brick_ranges(locs, shape, half, brick)
+    j = np.repeat(np.arange(n, dtype=np.int64), per)
     local = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
     cy, cx = cnt[j, 1], cnt[j, 2]
     iz, rem = local // (cy * cx), local % (cy * cx)
@@ -210,12 +225,83 @@ def roi_to_device(roi_mask, dev):
     return torch.from_numpy(host).to(dev), roi_mask.nbytes
 
 
-def labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size, out=None, stats=None):
+def check_planner(planner, device=True):
+    """ValueError, by name, for a planner that is not one of PLANNERS, and for the device
+    planner without a device"""
+    if planner not in PLANNERS:
+        raise ValueError("planner %r: 'host' (labels.plan_bricks, numpy) or 'device' "
+                         '(libfplplan.so)' % (planner,))
+    if planner == 'device' and device is None:
+        raise ValueError("planner='device' needs device=<int>: the host loop (device=None) "
+                         'plans nothing')
+    return planner
+
+
+class _DevicePlan:
+    """fplp_plan_bricks enqueued on a stream: the resident tables, the scratch that holds the
+    status word and a pinned copy of that word, valid once the stream is synchronised"""
+
+    def __init__(self, locs, shape, half, dev, stream):
+        torch = _torch()
+        self.n_index = plan_pairs(locs, shape, half)
+        nb = brick_counts(shape)
+        n_bricks = nb[0] * nb[1] * nb[2]
+        nbytes = _plancapi.scratch_bytes(len(locs), n_bricks, self.n_index)
+        self.tbars = torch.from_numpy(locs).to(dev) if len(locs) else None
+        self.offsets = torch.empty(n_bricks + 1, dtype=torch.int32, device=dev)
+        self.index = torch.empty(self.n_index, dtype=torch.int32, device=dev)
+        self.scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+        self.status = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        _plancapi.plan_bricks(0 if self.tbars is None else self.tbars.data_ptr(), len(locs),
+                              shape, half, self.offsets.data_ptr(),
+                              self.index.data_ptr() if self.n_index else 0, self.n_index,
+                              self.scratch.data_ptr(), self.scratch.numel() * 4,
+                              stream.cuda_stream)
+        self.status.copy_(self.scratch[:1], non_blocking=True)
+
+    def check(self):
+        """after the stream's synchronise: FplPlanError unless the status word is 0"""
+        if int(self.status[0]) != 0:
+            raise _plancapi.FplPlanError(
+                'fplp_plan_bricks: the device counted %d (T-bar, brick) pairs, plan_pairs %d; '
+                'the index was not written' % (int(self.offsets[-1]), self.n_index))
+
+
+def plan_bricks_device(locs, shape, half, device):
+    """plan_bricks on the device (libfplplan.so): resident int32 (offsets, index) tensors, equal
+    to plan_bricks's arrays byte for byte and complete when returned.  `locs`: the (N, 3)
+    table of plan_tbars; `device`: an int, True (the runtime's default device) or a
+    torch.device.  FplPlanError if the library is not built - no fallback to the host planner."""
+    torch = _torch()
+    if isinstance(device, torch.device):
+        _plancapi.load_library()
+        dev = device
+    else:
+        dev = _device.torch_device(device, 'device plan_bricks', _plancapi.load_library)
+    shape = check_shape(shape)
+    half = int(half)
+    if half < 0 or half > _plancapi.MAX_RADIUS:
+        raise ValueError('half %d must lie in [0, %d]' % (half, _plancapi.MAX_RADIUS))
+    locs = np.array(np.asarray(locs).reshape(-1, 3), np.int32)        # a writable copy
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        plan = _DevicePlan(locs, shape, half, dev, stream)
+        stream.synchronize()
+    plan.check()
+    return plan.offsets, plan.index
+
+
+def labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size, out=None, stats=None,
+                       planner='host'):
     """libfpllabels.so's kernel on a resident contiguous uint8 `roi` and the (N, 3) table of
     plan_tbars: resident uint8 (labels, mask), complete when returned.  `out`: a pair of
     contiguous uint8 tensors to write into.  `stats`: a dict that receives the upload bytes
-    of the tables and the planner's pair count."""
+    of the tables and the planner's pair count.  `planner`: 'host' builds the brick table
+    with plan_bricks and uploads it; 'device' uploads the T-bar table alone and builds the
+    brick table with libfplplan.so on the stream of the labels kernel (one synchronise;
+    FplPlanError if the status word it leaves is not 0)."""
     torch = _torch()
+    check_planner(planner)
     ru, ri = _radii(radius_use, radius_ign)
     if max(ru, ri) > _labelscapi.MAX_RADIUS:
         raise ValueError('radius %d exceeds the %d the kernel takes' % (max(ru, ri),
@@ -225,7 +311,10 @@ def labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size, out=None,
     shape = check_shape(roi.shape)
     dev = roi.device
     locs = _table(locs, shape, ru, ri)
-    offsets, index = plan_bricks(locs, shape, max(ru, ri))
+    if planner == 'device':
+        _plancapi.load_library()
+    else:
+        offsets, index = plan_bricks(locs, shape, max(ru, ri))
     if out is None:
         out = (torch.empty(shape, dtype=torch.uint8, device=dev),
                torch.empty(shape, dtype=torch.uint8, device=dev))
@@ -237,27 +326,43 @@ def labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size, out=None,
                              'shape on one device')
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        tables = [torch.from_numpy(a).to(dev) if a.size else None for a in (locs, offsets, index)]
-        ptr = [0 if t is None else t.data_ptr() for t in tables]
-        if not len(index):
+        if planner == 'device':
+            plan = _DevicePlan(locs, shape, max(ru, ri), dev, stream)
+            tables, pairs = [plan.tbars, plan.offsets, plan.index], plan.n_index
+            table_bytes = int(locs.nbytes)
+        else:
+            plan = None
+            tables = [torch.from_numpy(a).to(dev) if a.size else None
+                      for a in (locs, offsets, index)]
+            pairs = len(index)
+            table_bytes = int(locs.nbytes + offsets.nbytes + index.nbytes)
+        ptr = [0 if t is None or not t.numel() else t.data_ptr() for t in tables]
+        if not pairs:
             ptr[1] = 0
-        _labelscapi.labels_mask(roi.data_ptr(), ptr[0], len(locs), ptr[1], ptr[2], len(index),
+        _labelscapi.labels_mask(roi.data_ptr(), ptr[0], len(locs), ptr[1], ptr[2], pairs,
                                 shape, ru, ri, int(buffer_size), labels.data_ptr(),
                                 mask.data_ptr(), stream.cuda_stream)
         stream.synchronize()
+    if plan is not None:
+        plan.check()
     if stats is not None:
-        stats['table_bytes'] = int(locs.nbytes + offsets.nbytes + index.nbytes)
-        stats['pairs'] = int(len(index))
+        stats['table_bytes'] = table_bytes
+        stats['pairs'] = int(pairs)
     return labels, mask
 
 
-def write_labels_mask_device(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix, device):
+def write_labels_mask_device(tbars, roi_mask, radius_use, radius_ign, buffer_size, prefix, device,
+                             planner='host'):
     """the device route of fplsynapses.write_labels_mask: resident uint8 (labels, mask); with
-    `prefix` they are also downloaded and written as the host path writes them"""
+    `prefix` they are also downloaded and written as the host path writes them.  `planner`:
+    as labels_mask_device; a missing libfplplan.so is reported before a missing GPU."""
+    if check_planner(planner, device) == 'device':
+        _plancapi.load_library()
     dev = torch_device(device)
     roi, _ = roi_to_device(roi_mask, dev)
     locs = plan_tbars(tbars, roi.shape, radius_use, radius_ign)
-    labels, mask = labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size)
+    labels, mask = labels_mask_device(locs, roi, radius_use, radius_ign, buffer_size,
+                                      planner=planner)
     if prefix is not None:
         from . import keras_io
         ll, mm = labels.cpu().numpy(), mask.cpu().numpy()

@@ -32,7 +32,9 @@
             520^3 and 256^3, one T-bar per 16^3 voxels (the density of tools/example_flow.py),
             radii 3 / 6 and 6 / 12: the public call from a host roi_mask and from a resident
             one, the planners (plan_tbars + plan_bricks) alone, the kernel alone (HIP events;
-            GB/s at 3 B/voxel) and the bytes uploaded; written to profiles/labels.json
+            GB/s at 3 B/voxel) and the bytes uploaded; and the same with planner='device':
+            fplp_plan_bricks alone (HIP events), the public call from a host and from a
+            resident roi_mask, the bytes uploaded; written to profiles/labels.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -328,9 +330,41 @@ def labels_bench(ctx, torch, sizes=(520, 256), reps=5):
             k_ms = float(np.median(ms[3:]))
             row['kernel'] = dict(ms=k_ms, bytes_per_voxel=3, gb_s=3 * n ** 3 / k_ms / 1e6,
                                  timing='HIP events around one launch, median of %d' % (2 * reps))
+            # the device planner (libfplplan.so), same process, same inputs
+            row['device_planner_ms'], got_p = timed(lambda: fplsynapses.write_labels_mask(
+                tbars, roi, ru, ri, buf, None, device=ctx.device, planner='device'), reps)
+            row['device_planner_resident_roi_ms'], _ = timed(lambda: fplsynapses.write_labels_mask(
+                tbars, roi_d, ru, ri, buf, None, device=ctx.device, planner='device'), reps)
+            row['device_planner_identical'] = bool(torch.equal(got_p[0], got[0])
+                                                   and torch.equal(got_p[1], got[1]))
+            t_off, t_idx = labels.plan_bricks_device(table, shape, half, dev)
+            row['device_planner_tables_identical'] = bool(
+                np.array_equal(t_off.cpu().numpy(), offsets)
+                and np.array_equal(t_idx.cpu().numpy(), index))
+            row['upload_bytes_tables_device_planner'] = int(table.nbytes)
+            nbk = int(np.prod(labels.brick_counts(shape)))
+            nbytes = labels._plancapi.scratch_bytes(len(table), nbk, len(index))
+            scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+            ms = []
+            for i in range(3 + 2 * reps):
+                e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                e0.record()
+                labels._plancapi.plan_bricks(
+                    tabs[0].data_ptr(), len(table), shape, half, t_off.data_ptr(),
+                    t_idx.data_ptr(), len(index), scratch.data_ptr(), scratch.numel() * 4,
+                    torch.cuda.current_stream(dev).cuda_stream)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                ms.append(e0.elapsed_time(e1))
+            assert int(scratch[0].item()) == 0
+            row['planner_device_ms'] = float(np.median(ms[3:]))
+            row['planner_device_timing'] = ('HIP events around fplp_plan_bricks, median of %d'
+                                            % (2 * reps))
+            row['planner_device_scratch_bytes'] = int(nbytes)
+            row['plan_pairs_ms'] = timed(lambda: labels.plan_pairs(table, shape, half), reps)[0]
             print(json.dumps(row), flush=True)
             rows.append(row)
-            del got, roi_d, ll, mm, tabs
+            del got, got_p, roi_d, ll, mm, tabs, t_off, t_idx, scratch
     return rows
 
 
