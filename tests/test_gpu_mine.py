@@ -5,10 +5,13 @@ Voxel loss: equal as numbers (-0.0 == 0.0).  The device's double log is within 1
 double, so rounding it to float32 can - rarely - land on the other neighbour than the
 correctly rounded double log numpy takes: up to 1e-6 of the voxels may differ by one float32
 ulp, none by more.  Candidate rows and weights: exactly equal, in order."""
+import functools
+
 import numpy as np
 import pytest
 
-from flypylib_amd import fplobjdetect, mine
+from flypylib_amd import _minecapi, fplobjdetect, mine
+from tests import mine_cases
 from tests.mine_cases import mining_case as _mining_case, ulp_distance as _ulp_distance
 from tests.trained_fixture import blob_region, trained_network
 
@@ -148,6 +151,176 @@ def test_compaction_edge_cases(ctx):
     for shape in ((16, 16, 16), (16, 16, 32)):
         l4 = np.ones(shape, np.uint8)
         assert _candidates(l4, np.ones(shape, np.uint8), (0, 0, 0), 1, None) == int(np.prod(shape))
+
+
+# ---- more than 1024 chunks, more than one pass of the loss grid, capacity, short rows ------
+# (tests/mine_cases.py holds the shapes; tests/test_mine_host.py asserts on the CPU that each
+# reaches the path it is named for)
+
+@functools.lru_cache(maxsize=2)
+def _scan_case(name, cc=None):
+    """(pred, labels, mask, weights), built once for the runs of a case; no test writes to them"""
+    return mine_cases.scan_case(name, cc if name == 'scan_one_over' else None)
+
+
+@functools.lru_cache(maxsize=2)
+def _scan_rows(name, half, cc, weighted):
+    """candidates_numpy of a scan case"""
+    _, ll, mm, ww = _scan_case(name, cc if name == 'scan_one_over' else None)
+    want = mine.candidates_numpy(ll, mm, half, cc, ww if weighted else None)
+    for a in want[:3]:
+        a.setflags(write=False)
+    return want
+
+
+# the non-VEC kernels scan runs too: both classes of the short last run, and the forced ends
+MISALIGNED = [('scan_runs_2', (0, 2, 7), 0), ('scan_runs_2', (0, 2, 7), 1),
+              ('scan_one_over', (0, 0, 0), 1)]
+assert all(c in mine_cases.COMPACTION_CASES for c in MISALIGNED)
+
+
+@pytest.mark.parametrize('weighted', [False, True])
+@pytest.mark.parametrize('name,half,cc,misalign',
+                         [c + (False,) for c in mine_cases.COMPACTION_CASES] +
+                         [c + (True,) for c in MISALIGNED])
+def test_compaction_scans_runs_of_chunks(ctx, name, half, cc, misalign, weighted):
+    """more than 1024 chunks: a scan thread owns `per` > 1 chunks, the last one fewer, the
+    threads behind it none (scan_full: exactly one each)"""
+    _, ll, mm, ww = _scan_case(name, cc if name == 'scan_one_over' else None)
+    want = _scan_rows(name, half, cc, weighted)
+    held, runs = mine_cases.assert_runs_hold_candidates(name, half, weighted, *want[:3])
+    print('%s half %r class %d: %d rows, %d of %d runs must hold rows'
+          % (name, half, cc, len(want[0]), held, runs))
+    got = mine.candidates_device(_dev(ll, misalign), _dev(mm, misalign), half, cc,
+                                 _dev(ww, misalign) if weighted else None)
+    _assert_rows(got, want, (name, half, cc, weighted, misalign))
+    assert len(want[0]) > 10 * runs
+    if weighted:
+        assert want[3].dtype == np.float32 and (want[3] > 0).all()
+
+
+LOSS_EDGE = (9, 9, 12)
+
+
+@functools.lru_cache(maxsize=2)
+def _strided_loss(thresholds):
+    pred, ll, mm, _ = _scan_case('scan_runs_2')
+    want = mine.voxel_loss_numpy(pred, ll, mm, LOSS_EDGE, *thresholds)
+    want.setflags(write=False)
+    return want
+
+
+@pytest.mark.parametrize('misalign', [False, True])
+@pytest.mark.parametrize('thresholds', [(None, None), ((0.05, 2.0), (0.1, 0.5))])
+def test_voxel_loss_kernel_strides_over_a_volume_of_three_passes(ctx, thresholds, misalign):
+    """173 x 175 x 177: 1 339 669 groups of four against 524 288 lanes, so a lane takes the
+    loop body three times, or twice in the partial last pass, and the volume ends inside a
+    group.  `out` is pre-filled, so a voxel no pass reaches fails the comparison."""
+    shape = mine_cases.SCAN_SHAPES['scan_runs_2'][0]
+    pred, ll, mm, _ = _scan_case('scan_runs_2')
+    want = _strided_loss(thresholds)
+    got = mine.voxel_loss_device(_dev(pred, misalign), _dev(ll, misalign), _dev(mm, misalign),
+                                 LOSS_EDGE, *thresholds,
+                                 out=_dev(np.full(shape, 7, np.float32), misalign))
+    _assert_loss(got.cpu().numpy(), want,
+                 'voxel loss, 3 passes, %r%s' % (thresholds, ', misaligned' if misalign else ''))
+    flat, step = want.reshape(-1), mine_cases.PASS_VOXELS
+    assert mine_cases.scan_layout(shape)['passes'] == 3 and 2 * step < flat.size < 3 * step
+    for p in range(3):
+        part = flat[p * step:(p + 1) * step]
+        assert (part != 0).sum() > 0.2 * part.size and not (part == 7).any(), p
+
+
+def test_fill_writes_no_row_beyond_the_capacity(ctx):
+    """fplm_candidates_fill told of fewer rows than fplm_candidates_count found: the first
+    `capacity` rows as they are in the full table, every later element of every column as it
+    was"""
+    torch = _torch()
+    _, ll, mm = _mining_case(11, SHAPE)
+    ww = np.random.RandomState(3).uniform(-1, 1, SHAPE).astype(np.float32)
+    ww[::3] = 0
+    ww[5, 40, 50] = np.nan
+    half, cc = (12, 12, 12), 0
+    want = mine.candidates_numpy(ll, mm, half, cc, ww)
+    dev = torch.device('cuda', 0)
+    dl, dm, dw = _dev(ll), _dev(mm), _dev(ww)
+    nscr = _minecapi.scratch_bytes(ll.size)
+    scratch = torch.empty(nscr // 4, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    args = (dl.data_ptr(), dm.data_ptr(), dw.data_ptr(), SHAPE, half, cc, scratch.data_ptr(), nscr)
+    total = _minecapi.candidates_count(*args, stream.cuda_stream)
+    assert total == len(want[0]) > 2000
+
+    for capacity in (total - 1000, 1, total):
+        cols = torch.full((3, total), -7, dtype=torch.int32, device=dev)
+        w = torch.full((total,), -7.0, dtype=torch.float32, device=dev)
+        _minecapi.candidates_fill(*args, capacity, cols[0].data_ptr(), cols[1].data_ptr(),
+                                  cols[2].data_ptr(), w.data_ptr(), stream.cuda_stream)
+        stream.synchronize()
+        got = tuple(cols.cpu().numpy()) + (w.cpu().numpy(),)
+        _assert_rows([g[:capacity] for g in got], [c[:capacity] for c in want], ('capacity', capacity))
+        for g, col in zip(got, 'zyxw'):
+            assert (g[capacity:] == -7).all(), (capacity, col)
+
+
+def _short_row_inputs(i):
+    shape, border = mine_cases.SHORT_ROW_CASES[i]
+    pred, ll, mm = _mining_case(40 + i, shape)
+    ww = np.random.RandomState(50 + i).uniform(-0.3, 1, shape).astype(np.float32)
+    if mine_cases.SHORT_ROW_INSIDE[i] == 1:          # the centre voxel counts, for class 1
+        c = tuple(d // 2 for d in shape)
+        ll[c], mm[c], ww[c] = 1, 1, 0.5
+    return shape, border, pred, ll, mm, ww
+
+
+@pytest.mark.parametrize('misalign', [False, True])
+@pytest.mark.parametrize('i', range(len(mine_cases.SHORT_ROW_CASES)))
+def test_rows_shorter_than_a_group_and_borders_at_and_beyond_the_extent(ctx, i, misalign):
+    """X < 4: the four voxels of a lane lie in several rows and planes, and whether each is
+    inside the border is decided per voxel.  A border beyond the extent is clamped."""
+    shape, border, pred, ll, mm, ww = _short_row_inputs(i)
+    inside = mine_cases.SHORT_ROW_INSIDE[i]
+    for thresholds in ((None, None), ((0.05, 2.0), (0.1, 0.5))):
+        want = mine.voxel_loss_numpy(pred, ll, mm, border, *thresholds)
+        got = mine.voxel_loss_device(_dev(pred, misalign), _dev(ll, misalign), _dev(mm, misalign),
+                                     border, *thresholds,
+                                     out=_dev(np.full(shape, 7, np.float32), misalign))
+        _assert_loss(got.cpu().numpy(), want, 'voxel loss %r border %r' % (shape, border))
+        assert (want != 0).sum() <= inside
+    if inside > 1:
+        assert 0 < (want != 0).sum()
+    totals = [_candidates(ll, mm, border, cc, weights, misalign)
+              for cc in (0, 1) for weights in (None, ww)]
+    assert totals[0] + totals[2] <= inside and totals[1] <= totals[0] and totals[3] <= totals[2]
+    if inside > 1:
+        assert totals[0] > 0 and totals[1] > 0
+    if inside == 1:
+        assert totals == [0, 0, 1, 1] and (want != 0).sum() == 1
+    # every voxel inside the border, dense: the rows are the border's box
+    ones = np.ones(shape, np.uint8)
+    assert _candidates(ones, ones, border, 1, None, misalign) == inside
+
+
+@pytest.mark.parametrize('misalign', [False, True])
+@pytest.mark.parametrize('thresholds', [(None, None), ((0.05, 2.0), (0.1, 0.5))])
+def test_voxel_loss_of_predictions_off_the_unit_interval(ctx, thresholds, misalign):
+    """NaN, +-inf, -0.25, 1.5 and the exact 1 under both labels: voxel_loss_numpy is the
+    specification.  A NaN prediction is a NaN loss on both sides (np.maximum keeps it, and so
+    does the kernel's floor); everything else compares as usual."""
+    pred, ll, mm = mine_cases.off_unit_case()
+    with np.errstate(all='ignore'):
+        want = mine.voxel_loss_numpy(pred, ll, mm, (0, 0, 0), *thresholds)
+    got = mine.voxel_loss_device(_dev(pred, misalign), _dev(ll, misalign), _dev(mm, misalign),
+                                 (0, 0, 0), *thresholds,
+                                 out=_dev(np.full(pred.shape, 7, np.float32), misalign))
+    got = got.cpu().numpy()
+    nan = np.isnan(want)
+    assert nan.sum() == 4 and np.array_equal(np.isnan(pred), nan)
+    assert np.array_equal(np.isnan(got), nan)
+    got[nan], want[nan] = 0, 0
+    _assert_loss(got, want, 'voxel loss off the unit interval %r' % (thresholds,))
+    assert np.isinf(want).sum() == (2 if thresholds == (None, None) else 0)
+    assert np.array_equal(np.isinf(got), np.isinf(want)) and (want < 0).sum() == np.isinf(want).sum() * 2
 
 
 def _fixture():

@@ -9,6 +9,7 @@ import pytest
 
 from flypylib_amd import FplNetwork, _minecapi, batchgen, fplobjdetect, mine
 from tests import batchgen_cases as cases, side_abi_cases as abi
+from tests import mine_cases
 from tests.mine_cases import mining_case as _mining_case, ulp_distance as _ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -200,3 +201,112 @@ def test_new_arguments_default_to_todays_behaviour_and_refuse_misuse():
     a = np.array([0, 1, 2, 256, 257, -1], np.int64)
     assert mine.classes_u8(a).tolist() == [0, 1, 2, 2, 2, 2]
     assert mine.classes_u8(np.array([True, False])).tolist() == [1, 0]
+
+
+# ---- preflight of tests/test_gpu_mine.py's large and short-row cases -----------------------
+
+def test_the_named_constants_are_the_kernels():
+    src = open(os.path.join(ROOT, 'flypylib_amd', 'csrc', 'mine', 'mine.hip')).read()
+    for name, value in (('BLOCK', mine_cases.BLOCK), ('LANE_VOX', mine_cases.LANE_VOX),
+                        ('SCAN_THREADS', mine_cases.SCAN_THREADS)):
+        assert int(re.search(r'constexpr int %s = (\d+);' % name, src).group(1)) == value
+    assert re.search(r'std::min\(\(groups \+ BLOCK - 1\) / BLOCK, (\d+)u\)', src).group(1) \
+        == str(mine_cases.LOSS_GRID_CAP)
+    assert mine_cases.CHUNK == _minecapi.CHUNK == 4096
+    assert mine_cases.PASS_VOXELS == 2097152
+
+
+def test_every_scan_shape_reaches_its_path():
+    """n_chunks, per, the last thread with a run and that run's length, and the passes of the
+    loss grid, derived from the kernels' constants: a GPU test on one of these shapes cannot
+    pass by missing the path it is named for"""
+    lay = {n: mine_cases.scan_layout(s) for n, (s, _) in mine_cases.SCAN_SHAPES.items()}
+    threads = mine_cases.SCAN_THREADS
+
+    a = lay['scan_full']
+    assert (a['voxels'], a['n_chunks'], a['per']) == (4194304, 1024, 1)
+    assert (a['last_thread'], a['last_run'], a['last_chunk_voxels']) == (threads - 1, 1, 4096)
+
+    b = lay['scan_one_over']
+    assert (b['voxels'], b['n_chunks'], b['per']) == (4194305, 1025, 2)
+    assert (b['last_thread'], b['last_run'], b['last_chunk_voxels']) == (512, 1, 1)
+    # threads 513 .. 1023: lo = min(t * per, n_chunks) is n_chunks, the run is empty
+    assert all(min(t * b['per'], b['n_chunks']) == b['n_chunks'] for t in range(513, threads))
+    assert mine_cases.SCAN_SHAPES['scan_one_over'][0][1:] == (1, 1)      # a group spans four planes
+
+    c = lay['scan_runs_2']
+    assert (c['voxels'], c['n_chunks'], c['per']) == (5358675, 1309, 2)
+    assert (c['last_thread'], c['last_run']) == (654, 1)
+    assert c['groups'] == 1339669 and c['passes'] == 3
+    assert c['groups'] % (mine_cases.LOSS_GRID_CAP * mine_cases.BLOCK) != 0     # the last pass is partial
+    assert c['voxels'] % 4 == 3 and mine_cases.SCAN_SHAPES['scan_runs_2'][0][2] % 2 == 1
+
+    d = lay['scan_runs_3']
+    assert (d['voxels'], d['n_chunks'], d['per']) == (10217445, 2495, 3)
+    assert (d['last_thread'], d['last_run']) == (831, 2)
+
+    for n, l in lay.items():
+        # the layout is the kernel's: every chunk in exactly one run, runs in order
+        runs = [(min(t * l['per'], l['n_chunks']), min(min(t * l['per'], l['n_chunks']) + l['per'],
+                                                      l['n_chunks'])) for t in range(threads)]
+        assert runs[0][0] == 0 and all(p[1] == q[0] for p, q in zip(runs, runs[1:])), n
+        assert runs[l['last_thread']] == (l['n_chunks'] - l['last_run'], l['n_chunks']), n
+        assert all(lo == hi for lo, hi in runs[l['last_thread'] + 1:]), n
+        assert l['voxels'] <= _minecapi.MAX_VOXELS
+
+
+@pytest.mark.parametrize('name,half,cc', mine_cases.COMPACTION_CASES)
+def test_every_run_of_the_scan_cases_holds_candidates(name, half, cc):
+    _, ll, mm, ww = mine_cases.scan_case(name, cc)
+    shape = mine_cases.SCAN_SHAPES[name][0]
+    assert any(half) or name == 'scan_one_over'
+    for weights in (None, ww):
+        z, y, x, w = mine.candidates_numpy(ll, mm, half, cc, weights)
+        held, runs = mine_cases.assert_runs_hold_candidates(name, half, weights is not None, z, y, x)
+        print('%s half %r class %d %s: %d rows, %d of %d runs must hold rows'
+              % (name, half, cc, 'weighted' if w is not None else 'unweighted', len(z), held, runs))
+        assert runs == mine_cases.scan_layout(shape)['last_thread'] + 1
+        if name == 'scan_one_over' and not any(half):
+            n = shape[0]
+            assert (z[0], z[-1]) == (0, n - 1) and (w is None or (w[0], w[-1]) == (0.25, 0.25))
+    # every third plane has no weight (but scan_one_over's forced voxel 0), one weight is NaN
+    assert np.isnan(ww).sum() == 1 and not ww[3::3].any()
+    assert (ll == 3).any() and (mm == 2).any()
+
+
+def test_the_short_row_cases_select_what_they_are_named_for():
+    assert len(mine_cases.SHORT_ROW_CASES) == len(mine_cases.SHORT_ROW_INSIDE) == 7
+    for (shape, border), inside in zip(mine_cases.SHORT_ROW_CASES, mine_cases.SHORT_ROW_INSIDE):
+        ll, mm = np.zeros(shape, np.uint8), np.ones(shape, np.uint8)
+        z, y, x, _ = mine.candidates_numpy(ll, mm, border, 0)
+        assert len(z) == inside, (shape, border)
+        loss = mine.voxel_loss_numpy(np.full(shape, 0.5, np.float32), ll, mm, border)
+        assert int((loss != 0).sum()) == inside, (shape, border)
+        if inside == 1:
+            assert (z[0], y[0], x[0]) == tuple(d // 2 for d in shape)
+    # four of them have rows shorter than a group of four
+    assert sum(s[2] < mine_cases.LANE_VOX for s, _ in mine_cases.SHORT_ROW_CASES) == 4
+
+
+def test_the_off_unit_case_and_what_the_specification_makes_of_it():
+    """np.maximum keeps a NaN, so a NaN prediction gives a NaN loss under either label, with
+    and without thresholds; every other planted value gives a number"""
+    pred, ll, mm = mine_cases.off_unit_case()
+    nan = np.isnan(pred)
+    assert nan.sum() == 4 and set(ll[nan].tolist()) == {0, 1}
+    for v in mine_cases.OFF_UNIT[1:]:
+        assert set(ll[pred == np.float32(v)].tolist()) >= {0, 1}, v
+    floor = np.float32(-np.log(np.float64(np.float32(1e-8))))
+    with np.errstate(all='ignore'):
+        free = mine.voxel_loss_numpy(pred, ll, mm, (0, 0, 0))
+        clamped = mine.voxel_loss_numpy(pred, ll, mm, (0, 0, 0), (0.05, 2.0), (0.1, 0.5))
+    for loss in (free, clamped):
+        assert np.array_equal(np.isnan(loss), nan)
+    # label 0 at x = 0, 2, ..: +inf -> floor, -inf -> confident, -0.25 -> confident, 1.5 -> floor
+    assert free[4, 5, 2] == floor and free[4, 5, 4] == 0 and free[4, 5, 6] == 0
+    assert free[4, 5, 8] == floor and free[4, 5, 10] == floor
+    # label 1 at x = 1, 3, ..: +inf -> -inf, -inf -> floor, -0.25 -> floor, 1.5 -> -log 1.5, 1 -> 0
+    assert free[4, 5, 3] == -np.inf and free[4, 5, 5] == floor and free[4, 5, 7] == floor
+    assert free[4, 5, 9] == np.float32(-np.log(1.5)) and free[4, 5, 11] == 0
+    assert clamped[4, 5, 2] == 2.0 and clamped[4, 5, 3] == np.float32(0.1)
+    assert clamped[4, 5, 9] == np.float32(0.1) and clamped[4, 5, 11] == np.float32(0.1)
