@@ -20,6 +20,11 @@ STAGE_LIBRARIES holds rows of the same shape, built in the same way: libraries t
 stage of a side library rather than a device stage of their own (libfplplan.so plans the
 table libfpllabels.so's kernel reads).  They are a table of their own because SIDE_LIBRARIES
 is also the list of bindings _sidelib.bindings() / load_all() answer for, which stays as it is.
+
+EVAL_LIBRARIES is a third table of that shape, for what runs after training: libfplmatch.so
+finds the close pairs obj_pr / obj_pr_curve match.  It is no stage of the training round (the
+bindings SIDE_LIBRARIES lists) and serves no side library (STAGE_LIBRARIES), and both of those
+tables are pinned as they stand; its binding loads lazily, when an evaluation asks for a device.
 """
 import argparse
 import hashlib
@@ -42,6 +47,9 @@ SIDE_LIBRARIES = (
 )
 STAGE_LIBRARIES = (
     ('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),            # plan_bricks on the device
+)
+EVAL_LIBRARIES = (
+    ('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),        # obj_pr's close pairs
 )
 SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
@@ -161,15 +169,16 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in SIDE_LIBRARIES + STAGE_LIBRARIES:
+    for row in SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES or STAGE_LIBRARIES: same flags, same SHA-stamped rebuild, a
-    version script that exports the row's prefix only"""
-    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES + STAGE_LIBRARIES if r[0] == key)
+    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES or EVAL_LIBRARIES: same flags, same SHA-stamped
+    rebuild, a version script that exports the row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES
+                                       if r[0] == key)
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]

@@ -204,7 +204,7 @@ class FplNetwork:
         self._set_infer()
 
     # ---- full-volume inference (reference :136-189) -----------------------------
-    def infer(self, image, normalize=None, precision=None):
+    def infer(self, image, normalize=None, precision=None, device=None):
         """image: (Z,Y,X) array (already normalised float, as in the reference)
         or uint8 with `normalize=(mean, std)`; or an h5 path with dataset /main.
         Returns float32 predictions of the same shape; the rf_offset border
@@ -223,7 +223,17 @@ class FplNetwork:
         The returned array lives in memory recycled from earlier results that have died
         (`_capi.host_empty`: a fresh 520^3 result would cost 45 ms of first-touch page faults,
         three times the rest of the call); it is an ordinary writable ndarray, and a caller
-        that keeps it - or any slice of it - keeps its memory."""
+        that keeps it - or any slice of it - keeps its memory.
+
+        device=<int> or True (the runtime's default device): the prediction stays on the GPU
+        and is returned as a float32 torch tensor on that device - written there by the
+        executor when `device` is the network's own GPU, uploaded from the host result
+        otherwise (make_infer_parallel, another GPU).  Without torch or that GPU it raises."""
+        if device is not None:
+            from . import _device
+            _device.require_torch('device inference needs', 'use device=None for a host array')
+            dev = _device.torch_device(device, 'device inference', lambda: None)
+            return self._infer_resident(image, normalize, dev, precision)
         if isinstance(image, str):
             from . import keras_io
             image = np.load(image) if image.endswith('.npy') else keras_io.read_main(image)
@@ -308,6 +318,14 @@ class FplNetwork:
         if min(edge) < 1:
             raise ValueError('rf_size %r: the device voxel_loss needs a border of at least one '
                              'voxel (use device=None)' % (self.rf_size,))
+        pred = self._infer_resident(image, normalize, dev)
+        return mine.voxel_loss_device(pred, mine.to_device_u8(labels, dev),
+                                      mine.to_device_u8(mask, dev), edge, l0_thresh, l1_thresh)
+
+    def _infer_resident(self, image, normalize, dev, precision=None):
+        """the prediction of `image` as a float32 tensor on the torch device `dev`: inferred
+        into device memory when `dev` is this network's GPU, uploaded from the host otherwise"""
+        import torch
         if isinstance(image, str):
             from . import keras_io
             image = np.load(image) if image.endswith('.npy') else keras_io.read_main(image)
@@ -324,11 +342,11 @@ class FplNetwork:
             # returns when the context's stream has finished writing `pred`
             self.infer_network.program.infer_volume(
                 image, self.infer_sz, self.rf_offset, mean=mean, std=std,
-                precision=_PRECISIONS[self.precision], dst=pred)
+                precision=_PRECISIONS[precision or self.precision], dst=pred)
         else:
-            pred = torch.from_numpy(self.infer(image, normalize=normalize)).to(dev)
-        return mine.voxel_loss_device(pred, mine.to_device_u8(labels, dev),
-                                      mine.to_device_u8(mask, dev), edge, l0_thresh, l1_thresh)
+            pred = torch.from_numpy(self.infer(image, normalize=normalize,
+                                               precision=precision)).to(dev)
+        return pred
 
     # pickling: device handles never travel
     def __getstate__(self):

@@ -325,12 +325,62 @@ def obj_match(dists, allow_mult=False):
     return out
 
 
+MATCH_MODES = ('dense', 'sparse')
+
+
+def _sparse_mode(match, device):
+    """whether the call takes the sparse path; the keywords are checked by name"""
+    if match not in MATCH_MODES:
+        raise ValueError("match %r: 'dense' (the default) or 'sparse'" % (match,))
+    return match == 'sparse' or device is not None
+
+
+def _pair_table(predict_locs, groundtruth_locs, dist_thresh, device):
+    from . import match as fplmatch
+    if device is None:
+        return fplmatch.pairs_numpy(predict_locs, groundtruth_locs, dist_thresh)
+    return fplmatch.pairs_device(predict_locs, groundtruth_locs, dist_thresh, device)
+
+
+def _empty_pr(n_pred, n_gt):
+    return PR_Result(num_tp=0, tot_pred=n_pred, tot_gt=n_gt,
+                     pp=1 if n_pred == 0 else 0, rr=1 if n_gt == 0 else 0, match=None)
+
+
+def _pr_from_pairs(n_pred, n_gt, i, j, cost, allow_mult):
+    """PR_Result of obj_pr from the admissible pairs; `match` is a csr matrix"""
+    from . import match as fplmatch
+    if n_pred == 0 or n_gt == 0:
+        return _empty_pr(n_pred, n_gt)
+    match = fplmatch.match_sparse(n_pred, n_gt, i, j, cost, allow_mult)
+    num_tp = np.int64(match.nnz)
+    per_pred = np.diff(match.indptr).astype(np.int64)
+    extra = np.maximum(per_pred - 1, 0).sum()              # predictions matched twice
+    return PR_Result(num_tp=num_tp, tot_pred=n_pred + extra, tot_gt=n_gt,
+                     pp=num_tp / n_pred, rr=num_tp / n_gt, match=match)
+
+
 def obj_pr(predict_locs, groundtruth_locs, dist_thresh, predict_lbls=None,
-           groundtruth_lbls=None, allow_mult=False):
+           groundtruth_lbls=None, allow_mult=False, match='dense', device=None):
     """precision / recall of predicted vs ground-truth locations at a distance
     threshold (reference :323-376): pairs closer than `dist_thresh` (and, if labels are
-    given, with equal labels) are admissible, `obj_match` picks the matching"""
+    given, with equal labels) are admissible, `obj_match` picks the matching.
+
+    match='dense' (default) builds the N x M cost matrix, as the reference does.
+    match='sparse' finds the close pairs in row blocks (match.pairs_numpy), costs only those
+    and solves the matching per connected component (match.match_sparse): the same optimum
+    without the N x M matrix; `match` of the result is then a scipy csr matrix.  device=<int>
+    or True (the runtime's default device) implies sparse and takes the pair table from
+    libfplmatch.so's kernels; without torch, a GPU or the library it raises."""
     n_pred, n_gt = predict_locs.shape[0], groundtruth_locs.shape[0]
+    if _sparse_mode(match, device):
+        from . import match as fplmatch
+        if n_pred == 0 or n_gt == 0:
+            return _empty_pr(n_pred, n_gt)
+        i, j = _pair_table(predict_locs, groundtruth_locs, dist_thresh, device)
+        i, j, cost = fplmatch.pair_costs(predict_locs, groundtruth_locs, i, j, dist_thresh,
+                                         predict_lbls, groundtruth_lbls)
+        return _pr_from_pairs(n_pred, n_gt, i, j, cost, allow_mult)
     if n_pred == 0 or n_gt == 0:
         return PR_Result(num_tp=0, tot_pred=n_pred, tot_gt=n_gt,
                          pp=1 if n_pred == 0 else 0, rr=1 if n_gt == 0 else 0, match=None)
@@ -346,21 +396,59 @@ def obj_pr(predict_locs, groundtruth_locs, dist_thresh, predict_lbls=None,
                      pp=num_tp / n_pred, rr=num_tp / n_gt, match=match)
 
 
+def _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_lbls,
+                         groundtruth_lbls, allow_mult, device):
+    """obj_pr per confidence threshold from ONE pair table: built over the predictions that
+    pass the lowest threshold, then per threshold its rows filtered and renumbered"""
+    from . import match as fplmatch
+    thresholds = np.asarray(thresholds).reshape(-1)
+    if thresholds.size == 0:
+        return []
+    conf, gt_locs = np.asarray(predict['conf']), groundtruth['locs']
+    n_gt = gt_locs.shape[0]
+    base = conf >= thresholds.min()
+    locs, conf = predict['locs'][base, :], conf[base]
+    lbls = None if predict_lbls is None else predict_lbls[base]
+    if locs.shape[0] and n_gt:
+        i, j = _pair_table(locs, gt_locs, dist_thresh, device)
+        i, j, cost = fplmatch.pair_costs(locs, gt_locs, i, j, dist_thresh, lbls, groundtruth_lbls)
+    points = []
+    for thd in thresholds:
+        sel = conf >= thd
+        n_sel = int(sel.sum())
+        if n_sel == 0 or n_gt == 0:
+            points.append(_empty_pr(n_sel, n_gt))
+            continue
+        renumber = np.cumsum(sel) - 1
+        keep = sel[i]
+        points.append(_pr_from_pairs(n_sel, n_gt, renumber[i[keep]], j[keep], cost[keep],
+                                     allow_mult))
+    return points
+
+
 def obj_pr_curve(predict, groundtruth, dist_thresh, thresholds, predict_lbls=None,
-                 groundtruth_lbls=None, allow_mult=False):
+                 groundtruth_lbls=None, allow_mult=False, match='dense', device=None):
     """precision / recall at each confidence threshold (reference :378-436); `predict`
-    / `groundtruth` are {'locs','conf'} dicts or json files"""
+    / `groundtruth` are {'locs','conf'} dicts or json files.
+
+    match / device: as for obj_pr.  In sparse mode the pair table is built once, over the
+    predictions that pass the lowest threshold, and filtered per threshold; the results are
+    those of obj_pr called per threshold."""
     from . import fplsynapses
     if isinstance(predict, str):
         predict = fplsynapses.load_from_json(predict)
     if isinstance(groundtruth, str):
         groundtruth = fplsynapses.load_from_json(groundtruth)
-    points = []
-    for thd in np.asarray(thresholds).reshape(-1):
-        sel = predict['conf'] >= thd
-        points.append(obj_pr(predict['locs'][sel, :], groundtruth['locs'], dist_thresh,
-                             None if predict_lbls is None else predict_lbls[sel],
-                             groundtruth_lbls, allow_mult=allow_mult))
+    if _sparse_mode(match, device):
+        points = _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_lbls,
+                                      groundtruth_lbls, allow_mult, device)
+    else:
+        points = []
+        for thd in np.asarray(thresholds).reshape(-1):
+            sel = predict['conf'] >= thd
+            points.append(obj_pr(predict['locs'][sel, :], groundtruth['locs'], dist_thresh,
+                                 None if predict_lbls is None else predict_lbls[sel],
+                                 groundtruth_lbls, allow_mult=allow_mult))
 
     def column(name):
         return np.array([getattr(pt, name) for pt in points], dtype=np.float64)
@@ -466,19 +554,34 @@ def _gen_volume_host(train_data, context_sz, batch_sz, ratio, rng=None):
 
 def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigma=5,
                        volume_offset=(0, 0, 0), buffer_sz=5, allow_mult=False,
-                       normalize=None):
+                       normalize=None, device=None):
     """precision / recall curves of a network on labelled substacks (reference
     :463-523): per substack [image, ground-truth json (, segmentation)] -> infer ->
     voxel2obj -> obj_pr_curve against the json's T-bars (buffer applied to both), then
     the aggregate.  The reference forks a post-processing worker per substack; here
-    inference and voxel2obj share the GPU, so substacks run in order."""
+    inference and voxel2obj share the GPU, so substacks run in order.
+
+    device=<int> or True (the runtime's default device): the prediction is inferred into a
+    resident float32 tensor (FplNetwork.infer(device=...)), voxel2obj reads it where it lies
+    and obj_pr_curve(device=...) scores the points on the sparse pair table of
+    libfplmatch.so; the segmentation lookup stays on the host.  The results equal the host
+    call's.  Without torch, a GPU or the library the call raises."""
     from . import fplsynapses
     thds = np.asarray(thds)
+    dev = None
+    if device is not None:
+        from . import match as fplmatch
+        dev = fplmatch.torch_device(device)
     results = []
     for ss in substacks:
-        pred = network.infer(ss[0], normalize=normalize)
-        out = voxel2obj(pred, obj_min_dist, smoothing_sigma, volume_offset, buffer_sz)
-        gt = fplsynapses.load_from_json(ss[1], pred.shape, buffer_sz)
+        if dev is None:
+            pred = network.infer(ss[0], normalize=normalize)
+            out = voxel2obj(pred, obj_min_dist, smoothing_sigma, volume_offset, buffer_sz)
+        else:
+            pred = network.infer(ss[0], normalize=normalize, device=dev.index)
+            out = voxel2obj(pred, obj_min_dist, smoothing_sigma, volume_offset, buffer_sz,
+                            device=dev.index)
+        gt = fplsynapses.load_from_json(ss[1], tuple(pred.shape), buffer_sz)
         lbls_pd = lbls_gt = None
         if len(ss) >= 3 and ss[2] is not None:
             seg = np.asarray(_load_main(ss[2]))
@@ -488,7 +591,8 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
                 return seg[ind[:, 2], ind[:, 1], ind[:, 0]]
             lbls_pd, lbls_gt = labels_at(out), labels_at(gt)
         results.append(obj_pr_curve(out, gt, obj_min_dist, thds, lbls_pd, lbls_gt,
-                                    allow_mult=allow_mult))
+                                    allow_mult=allow_mult,
+                                    **({} if dev is None else {'device': dev.index})))
     return aggregate_pr(results), results
 
 

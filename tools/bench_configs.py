@@ -35,6 +35,12 @@
             GB/s at 3 B/voxel) and the bytes uploaded; and the same with planner='device':
             fplp_plan_bricks alone (HIP events), the public call from a host and from a
             resident roi_mask, the bytes uploaded; written to profiles/labels.json
+  match     obj_pr_curve's matching, all in one process: 3307 x 3000 points in a 520^3 cube at
+            the example script's 18 confidence thresholds - the dense default, match='sparse'
+            and device=... - with the kernels of libfplmatch.so alone (count + scan and fill by
+            HIP events, each kernel by the profiler where it answers) and the rows downloaded;
+            and 10^5 x 10^5 points in a 4096^3 box, sparse host against device only (the dense
+            matrix would be 80 GB and is not run); written to profiles/match.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -255,6 +261,133 @@ def mine_bench(ctx, torch, n=520, reps=5):
         print(json.dumps({name: tables[name]}), flush=True)
         del ph, pd
     out['tables'] = tables
+    return out
+
+
+def match_bench(ctx, torch, reps=5):
+    """obj_pr_curve: the dense default against match='sparse' and device=..."""
+    from flypylib_amd import _matchcapi, fplobjdetect, match
+    dev = torch.device('cuda', ctx.device)
+    t_match = 27
+    thds = np.arange(0.6, 0.96, 0.02)               # the example script's 18 thresholds
+
+    def points(seed, n_gt, n_hit, n_fp, box):
+        rs = np.random.RandomState(seed)
+        gt = rs.rand(n_gt, 3) * box
+        pred = np.concatenate([gt[:n_hit] + rs.randn(n_hit, 3) * 4, rs.rand(n_fp, 3) * box])
+        return {'locs': pred, 'conf': 0.6 + 0.4 * rs.rand(len(pred))}, {'locs': gt}
+
+    def timed(fn, k):
+        ts = []
+        for _ in range(k):
+            t0 = time.perf_counter()
+            r = fn()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3, r
+
+    def kernels(pred, gt):
+        """count + scan and fill by HIP events around the two entry points; the three kernels
+        one by one from the profiler, or None where it does not report them"""
+        n, m, t2 = len(pred), len(gt), match.threshold2(t_match)
+        nscr = _matchcapi.scratch_bytes(n, m)
+        p_dev, g_dev = torch.from_numpy(pred).to(dev), torch.from_numpy(gt).to(dev)
+        scratch = torch.empty((nscr + 7) // 8, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        args = (p_dev.data_ptr(), n, g_dev.data_ptr(), m, t2, scratch.data_ptr(), nscr)
+        total = _matchcapi.pairs_count(*args, stream.cuda_stream)
+        cols = torch.empty((2, total), dtype=torch.int32, device=dev)
+
+        def fill():
+            _matchcapi.pairs_fill(*args, total, cols[0].data_ptr(), cols[1].data_ptr(),
+                                  stream.cuda_stream)
+        fill()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        count_ms, fill_ms = [], []
+        for _ in range(reps):
+            ev[0].record(stream)
+            _matchcapi.pairs_count(*args, stream.cuda_stream)
+            ev[1].record(stream)
+            fill()
+            ev[2].record(stream)
+            stream.synchronize()
+            count_ms.append(ev[0].elapsed_time(ev[1]))
+            fill_ms.append(ev[1].elapsed_time(ev[2]))
+        res = {'rows': int(total), 'segments': _matchcapi.segments(n, m),
+               'count_and_scan_ms': float(np.median(count_ms)), 'fill_ms': float(np.median(fill_ms)),
+               'pair_tests': n * m}
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                _matchcapi.pairs_count(*args, stream.cuda_stream)
+                fill()
+                stream.synchronize()
+            each = {}
+            for e in prof.key_averages():
+                for k in ('count_kernel', 'scan_kernel', 'fill_kernel'):
+                    if k in e.key:
+                        us = getattr(e, 'device_time_total', None)
+                        if us is None:
+                            us = getattr(e, 'cuda_time_total', 0.0)
+                        each[k + '_ms'] = us / 1e3 / max(1, e.count)
+            res['profiler'] = each or None
+        except Exception as e:      # noqa: BLE001
+            res['profiler'] = None
+            res['profiler_error'] = '%s: %s' % (type(e).__name__, e)
+        return res
+
+    def same(a, b):
+        return all(np.array_equal(getattr(a, f), getattr(b, f))
+                   for f in ('num_tp', 'tot_pred', 'tot_gt', 'pp', 'rr'))
+
+    out = {'thresholds': len(thds), 'dist_thresh': t_match, 'reps': reps}
+    # one substack of the example: 3307 predictions, 3000 T-bars in a 520^3 cube
+    p, g = points(0, 3000, 2800, 507, 520.0)
+    curve = fplobjdetect.obj_pr_curve
+    fplobjdetect.obj_pr_curve(p, g, t_match, thds[-2:], device=ctx.device)       # warm-up
+    t_dense, r_dense = timed(lambda: curve(p, g, t_match, thds), 1)
+    print('match: dense %.0f ms' % t_dense, flush=True)
+    t_sparse, r_sparse = timed(lambda: curve(p, g, t_match, thds, match='sparse'), reps)
+    t_dev, r_dev = timed(lambda: curve(p, g, t_match, thds, device=ctx.device), reps)
+    t_np, _ = timed(lambda: match.pairs_numpy(p['locs'], g['locs'], t_match), reps)
+    t_pd, _ = timed(lambda: match.pairs_device(p['locs'], g['locs'], t_match, ctx.device), reps)
+    out['substack'] = {
+        'points': [len(p['locs']), len(g['locs'])], 'box': 520,
+        'obj_pr_curve_dense_ms': t_dense, 'obj_pr_curve_sparse_ms': t_sparse,
+        'obj_pr_curve_device_ms': t_dev, 'dense_over_sparse': t_dense / t_sparse,
+        'dense_over_device': t_dense / t_dev, 'pairs_numpy_ms': t_np, 'pairs_device_ms': t_pd,
+        'equal_results': bool(same(r_dense, r_sparse) and same(r_dense, r_dev)),
+        'kernels': kernels(p['locs'], g['locs'])}
+    print(json.dumps(out['substack']), flush=True)
+    # a whole ROI: 10^5 x 10^5 points in a 4096^3 box
+    p, g = points(1, 100000, 90000, 10000, 4096.0)
+    t_pd, tab = timed(lambda: match.pairs_device(p['locs'], g['locs'], t_match, ctx.device), reps)
+    t_dev, r_dev = timed(lambda: curve(p, g, t_match, thds, device=ctx.device), 3)
+    print('match: roi device %.0f ms' % t_dev, flush=True)
+    # the host table is two minutes of numpy: built once, inside the curve, and timed there
+    host_table = {}
+    real = match.pairs_numpy
+
+    def pairs_timed(*a):
+        t0 = time.perf_counter()
+        host_table['table'] = real(*a)
+        host_table['ms'] = (time.perf_counter() - t0) * 1e3
+        return host_table['table']
+    match.pairs_numpy = pairs_timed
+    try:
+        t_sparse, r_sparse = timed(lambda: curve(p, g, t_match, thds, match='sparse'), 1)
+    finally:
+        match.pairs_numpy = real
+    t_np, tab_np = host_table['ms'], host_table['table']
+    out['roi'] = {
+        'points': [len(p['locs']), len(g['locs'])], 'box': 4096,
+        'obj_pr_curve_dense_ms': None,
+        'dense_note': 'not run: the dense cost matrix alone is 80 GB',
+        'obj_pr_curve_sparse_ms': t_sparse, 'obj_pr_curve_device_ms': t_dev,
+        'sparse_over_device': t_sparse / t_dev, 'pairs_numpy_ms': t_np, 'pairs_device_ms': t_pd,
+        'equal_tables': bool(np.array_equal(tab[0], tab_np[0]) and np.array_equal(tab[1], tab_np[1])),
+        'equal_results': bool(same(r_sparse, r_dev)),
+        'kernels': kernels(p['locs'], g['locs'])}
+    print(json.dumps(out['roi']), flush=True)
     return out
 
 
@@ -558,6 +691,11 @@ def main():
         res['mine'] = mine_bench(ctx, torch, a.mine_size)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'mine.json')
+
+    if 'match' in what:
+        res['match'] = match_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'match.json')
 
     if 'labels' in what:
         res['labels'] = labels_bench(ctx, torch)
