@@ -25,6 +25,10 @@ EVAL_LIBRARIES is a third table of that shape, for what runs after training: lib
 finds the close pairs obj_pr / obj_pr_curve match.  It is no stage of the training round (the
 bindings SIDE_LIBRARIES lists) and serves no side library (STAGE_LIBRARIES), and both of those
 tables are pinned as they stand; its binding loads lazily, when an evaluation asks for a device.
+
+POST_LIBRARIES is a fourth table of that shape, for what runs after the pipeline: libfplnear.so
+finds the close pairs within full_roi_inference's point list, which rm_tbar_multi_pred merges.
+The three tables above are pinned by their tests; its binding loads lazily as well.
 """
 import argparse
 import hashlib
@@ -51,6 +55,10 @@ STAGE_LIBRARIES = (
 EVAL_LIBRARIES = (
     ('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),        # obj_pr's close pairs
 )
+POST_LIBRARIES = (
+    ('near', 'near', 'fpln', 'fplnear.h', 'libfplnear.so'),            # rm_tbar_multi_pred's close pairs
+)
+ALL_TABLES = SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES + POST_LIBRARIES
 SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
@@ -169,16 +177,15 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES:
+    for row in ALL_TABLES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES or EVAL_LIBRARIES: same flags, same SHA-stamped
-    rebuild, a version script that exports the row's prefix only"""
-    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES
-                                       if r[0] == key)
+    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES or POST_LIBRARIES: same flags,
+    same SHA-stamped rebuild, a version script that exports the row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in ALL_TABLES if r[0] == key)
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]

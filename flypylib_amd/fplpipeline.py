@@ -266,12 +266,20 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
                        local_cache_dir=None,
                        roi_force_file=False,
                        instance_name='grayscale',
-                       dvid_seg_info=None, precision=None, timings=None):
+                       dvid_seg_info=None, precision=None, timings=None,
+                       neighbor_thresh=None, merge_method='sparse', merge_device=None):
     """Predictions of a trained network within the substacks of an ROI, cached per
     substack in `working_dir` (reference :841-986; same arguments).  `dvid_roi` is
     an ROI text file (`roi_from_txt`) or a list of `szyx`; `precision` overrides the
     network's ('f32' / 'bf16').  Returns {'locs': (N,3) x/y/z, 'conf': (N,)} (all
-    ranks return the merged result once every rank's substacks are on disk)."""
+    ranks return the merged result once every rank's substacks are on disk).
+
+    neighbor_thresh=None (default): nothing more.  With a number, the rank that writes `all.p`
+    then merges the detections two neighbouring substacks both made of one T-bar
+    (fplsynapses.rm_tbar_multi_pred with method=`merge_method`, device=`merge_device`, and
+    merge_multi_pred), writes the merged list to `all_merged.p` beside it and returns it; the
+    other ranks return the unmerged list.  With a segmentation (`dvid_seg_info`) the points'
+    labels are read from it at the rounded locations, else all labels are equal."""
     # the reference reads a 'segmentation' labelmap from a second DVID node
     # (dvid_seg_info = [server, uuid]); here it is a label volume with the image's
     # extents: array-like or 'npy://file'
@@ -486,7 +494,26 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
     elif rank == 0:
         with open('%s/all.p' % working_dir, 'wb') as f_out:
             pickle.dump(obj, f_out)
+        if neighbor_thresh is not None:
+            obj = merge_border_duplicates(obj, neighbor_thresh, seg_src, merge_method, merge_device)
+            with open('%s/all_merged.p' % working_dir, 'wb') as f_out:
+                pickle.dump(obj, f_out)
     return obj
+
+
+def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse', device=None):
+    """the point list with the duplicates along substack borders merged: rm_tbar_multi_pred and
+    merge_multi_pred.  `seg_src`, an array source of segment ids with the image's extents,
+    gives the points' labels at their rounded (x, y, z), clipped into the volume."""
+    from . import fplsynapses
+    labels = None
+    if seg_src is not None and len(tbars['conf']):
+        at = np.clip(np.round(tbars['locs']).astype(np.int64)[:, ::-1], 0,
+                     np.asarray(seg_src.extent) - 1)
+        labels = np.asarray(seg_src.arr[at[:, 0], at[:, 1], at[:, 2]])
+    found = fplsynapses.rm_tbar_multi_pred(tbars, neighbor_thresh=neighbor_thresh, labels=labels,
+                                           method=method, device=device)
+    return fplsynapses.merge_multi_pred(tbars, *found)
 
 
 def fplobjdetect_precision(network, precision):

@@ -1,6 +1,7 @@
 """Synapse (T-bar) point lists as JSON - the data formats on the output side of the
 detection path (reference `flypylib/fplsynapses.py:11-111`) - and the label / mask
-volumes training is fed from (`write_labels_mask`, :251-310).  The DVID push / ROI /
+volumes training is fed from (`write_labels_mask`, :251-310), and the merging of duplicate
+detections along substack borders (`rm_tbar_multi_pred`, :378-449).  The DVID push / ROI /
 annotation-editing helpers of the reference need `libdvid` and are not part of this
 package."""
 import json
@@ -138,3 +139,207 @@ def write_labels_mask(tbars, roi_mask, radius_use, radius_ign, buffer_size, pref
         keras_io.write_main('%s_labels.h5' % prefix, labels)
         keras_io.write_main('%s_mask.h5' % prefix, mask)
     return labels, mask
+
+
+def _multi_pred_labels(tbars_in, segm_name, labels):
+    n = np.asarray(tbars_in['conf']).shape[0]
+    if labels is not None:
+        labels = np.asarray(labels).reshape(-1)
+        if labels.shape[0] != n:
+            raise ValueError('labels holds %d entries for %d points' % (labels.shape[0], n))
+        return labels
+    if segm_name:
+        raise ValueError('segm_name=%r: reading labels from DVID is out of scope here; pass the '
+                         "points' labels as an array, labels=" % (segm_name,))
+    return np.zeros(np.asarray(tbars_in['conf']).shape)
+
+
+def _multi_pred_dense(pos, conf, ll, neighbor_thresh):
+    """the reference loop (:386-449), matrix included"""
+    dists = np.sqrt((
+        (pos.reshape((-1, 1, 3)) - pos.reshape((1, -1, 3))) ** 2).sum(
+            axis=2))
+
+    has_neighbor = np.sum((dists > 0) & (dists < neighbor_thresh),
+                          axis=1)
+    tt_idx = np.argsort(-conf)
+
+    rm_idx = np.zeros(tt_idx.shape, 'bool')
+    mv_idx = np.zeros(tt_idx.shape, 'bool')
+    mv_loc = np.zeros(pos.shape, 'int')
+
+    for ii in tt_idx:
+        if rm_idx[ii]:
+            continue
+        if not has_neighbor[ii]:
+            continue
+
+        candidates = (
+            (dists[ii, :] > 0) & (dists[ii, :] < neighbor_thresh) &
+            (ll == ll[ii]) &
+            (np.logical_not(rm_idx)))
+
+        jj = np.nonzero(candidates)[0]
+
+        if jj.size > 0:
+            mv_idx[ii] = True
+
+            old_loc = pos[ii, :]
+            candidates[ii] = True
+            while True:
+                # new location by interpolation
+                ww = conf * candidates
+                ww = ww / np.sum(ww)
+
+                mv_loc[ii, :] = np.round(
+                    np.sum(ww.reshape((-1, 1)) * pos, axis=0))
+                if np.array_equal(old_loc, mv_loc[ii, :]):
+                    break
+
+                old_loc = mv_loc[ii, :].copy()
+                new_dists = np.sqrt(np.sum(
+                    (pos - mv_loc[ii, :]) ** 2, axis=1))
+
+                candidates = (
+                    (new_dists < neighbor_thresh) &
+                    (ll == ll[ii]) &
+                    (np.logical_not(rm_idx)))
+
+            jj = np.nonzero(candidates)[0]
+            rm_idx[jj] = True
+
+    rm_idx[mv_idx] = False
+
+    return rm_idx, mv_idx, mv_loc
+
+
+def _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device):
+    """the same loop on the neighbour table of near.py and a host cell grid: no N x N object"""
+    from . import near
+    n = pos.shape[0]
+    if n == 0:
+        return np.zeros(0, 'bool'), np.zeros(0, 'bool'), np.zeros(pos.shape, 'int')
+    if device is None:
+        indptr, indices = near.pairs_numpy(pos, neighbor_thresh)
+    else:
+        indptr, indices = near.pairs_device(pos, neighbor_thresh, device)
+    # the table is a superset (s <= T2): keep what the reference's own expression keeps
+    keep = np.zeros(len(indices), bool)
+    owner = np.repeat(np.arange(n), np.diff(indptr))
+    step = 1 << 20
+    for a in range(0, len(indices), step):
+        d = np.sqrt(((pos[owner[a:a + step]] - pos[indices[a:a + step]]) ** 2).sum(axis=1))
+        keep[a:a + step] = (d > 0) & (d < neighbor_thresh)
+    has_neighbor = np.bincount(owner[keep], minlength=n)
+    indices = indices[keep]
+    indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(has_neighbor, out=indptr[1:])
+    del owner, keep
+    grid = near.CellGrid(pos, neighbor_thresh)
+
+    tt_idx = np.argsort(-conf)
+
+    rm_idx = np.zeros(tt_idx.shape, 'bool')
+    mv_idx = np.zeros(tt_idx.shape, 'bool')
+    mv_loc = np.zeros(pos.shape, 'int')
+
+    for ii in tt_idx[has_neighbor[tt_idx] > 0]:
+        if rm_idx[ii]:
+            continue
+
+        row = indices[indptr[ii]:indptr[ii + 1]]
+        jj = row[(ll[row] == ll[ii]) & np.logical_not(rm_idx[row])]
+
+        if jj.size > 0:
+            mv_idx[ii] = True
+
+            old_loc = pos[ii, :]
+            at = np.searchsorted(jj, ii)
+            cand = np.concatenate([jj[:at], [ii], jj[at:]])      # ascending, ii among them
+            while True:
+                # new location by interpolation, over the candidates alone, in index order
+                if cand.size:
+                    ww = conf[cand]
+                    ww = ww / np.sum(ww)
+                    rows = ww.reshape((-1, 1)) * pos[cand]
+                    mean = rows[0]
+                    for r in rows[1:]:
+                        mean = mean + r
+                else:
+                    mean = np.full(3, np.nan)        # the reference's 0 / 0
+                mv_loc[ii, :] = np.round(mean)
+                if np.array_equal(old_loc, mv_loc[ii, :]):
+                    break
+
+                old_loc = mv_loc[ii, :].copy()
+                # a ball around the moved centre may hold points that are partners of no
+                # candidate: asked of the grid, not of the table
+                ball = grid.ball(mv_loc[ii, :])
+                new_dists = np.sqrt(np.sum(
+                    (pos[ball] - mv_loc[ii, :]) ** 2, axis=1))
+                cand = ball[(new_dists < neighbor_thresh) &
+                            (ll[ball] == ll[ii]) &
+                            (np.logical_not(rm_idx[ball]))]
+
+            rm_idx[cand] = True
+
+    rm_idx[mv_idx] = False
+
+    return rm_idx, mv_idx, mv_loc
+
+
+def rm_tbar_multi_pred(tbars_in, dvid_node=None, segm_name=None, neighbor_thresh=30, labels=None,
+                       method='dense', device=None):
+    """Detections of one T-bar made twice, by two neighbouring substacks (reference :378-449).
+    In order of falling confidence, a point that has not been removed gathers the points of
+    its own segment closer than `neighbor_thresh`, moves to their confidence-weighted mean
+    (rounded, and again from the points around the moved centre until it rests) and marks
+    them for removal.  -> (rm_idx, mv_idx, mv_loc): bool (N,) removed, bool (N,) moved,
+    'int' (N, 3) the new locations of the moved points; merge_multi_pred applies them.
+
+    Labels: `labels`, an array of N segment ids, stands in for the reference's DVID query.
+    Without it and with a falsy `segm_name` all labels are equal (the reference's np.zeros
+    branch); a truthy `segm_name` without `labels` is a ValueError - DVID is out of scope.
+
+    method='dense' (default) restates the reference loop, its N x N distance matrix included:
+    it is the specification, quirks and all - coincident points are no neighbours at first but
+    are candidates around a moved centre; has_neighbor ignores labels; a moved point is never
+    removed.  The matrix is 8 N^2 bytes: 7 GB at 30 000 points.
+
+    method='sparse' returns the same three arrays without any N x N object.  The first
+    candidate set of a point is its row of the neighbour table (near.pairs_numpy, a superset
+    filtered by the reference's own sqrt expression); the balls around moved centres are asked
+    of a host cell grid (near.CellGrid) and filtered by the reference's expression; the
+    weighted mean runs over the candidates alone in ascending index order, which is the order
+    of the reference's axis-0 sum with its zero rows left out.
+    One difference is known: the reference divides by np.sum(ww), a pairwise sum over all N
+    entries whose last bit depends on where the candidates sit in the array.  The two methods
+    are bit-equal whenever the sum of the candidates' confidences is exact in float64 - true
+    of the float32-valued confidences voxel2obj returns from float32 predictions unless they
+    span more than about 2^29 in magnitude.  Otherwise the divisor can differ in its last bit,
+    which changes a result only where a mean coordinate lies within an ulp of a half-integer.
+
+    device=<int> (or True, the runtime's default device), with method='sparse' only, takes the
+    table from libfplnear.so (near.pairs_device: the same bytes); device=None builds it on the
+    host.  No host fallback: a missing library raises.  Anything else is a ValueError."""
+    if method not in ('dense', 'sparse'):
+        raise ValueError("method %r: 'dense' (the reference's matrix) or 'sparse'" % (method,))
+    if device is not None and method != 'sparse':
+        raise ValueError("device=%r needs method='sparse': the dense method is the host "
+                         'specification' % (device,))
+    ll = _multi_pred_labels(tbars_in, segm_name, labels)
+    pos, conf = tbars_in['locs'], tbars_in['conf']
+    if method == 'dense':
+        return _multi_pred_dense(pos, conf, ll, neighbor_thresh)
+    return _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device)
+
+
+def merge_multi_pred(tbars, rm_idx, mv_idx, mv_loc):
+    """the point list after rm_tbar_multi_pred: moved points take their `mv_loc`, removed
+    points are dropped, the order is otherwise kept.  -> a new {'locs', 'conf'} of the input's
+    dtypes"""
+    rm_idx, mv_idx = np.asarray(rm_idx, bool), np.asarray(mv_idx, bool)
+    locs = np.array(tbars['locs'], copy=True)
+    locs[mv_idx] = np.asarray(mv_loc)[mv_idx]
+    keep = np.logical_not(rm_idx)
+    return {'locs': locs[keep], 'conf': np.asarray(tbars['conf'])[keep]}

@@ -41,6 +41,14 @@
             HIP events, each kernel by the profiler where it answers) and the rows downloaded;
             and 10^5 x 10^5 points in a 4096^3 box, sparse host against device only (the dense
             matrix would be 80 GB and is not run); written to profiles/match.json
+  dedupe    fplsynapses.rm_tbar_multi_pred on a synthetic T-bar list with planted border
+            duplicates - a lattice of spacing 34 (3 300 T-bars per 512^3, the 1536^3 run's
+            density) jittered by +-2, every point within 10 voxels of a z plane 512 apart
+            detected twice, float32-valued confidences - at N = 3 000, 10^5 and 10^6, all in one
+            process: the neighbour table on the host (near.pairs_numpy) and on the GPU
+            (near.pairs_device; the whole call, and the key kernel, torch.sort, count + scan
+            and fill alone by HIP events), and the whole call per method (dense at 3 000 only);
+            median, min and max over --dedupe-reps runs; written to profiles/dedupe.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -391,6 +399,111 @@ def match_bench(ctx, torch, reps=5):
     return out
 
 
+def dedupe_points(n, seed=0, spacing=34.0, jitter=2, near_plane=10.0, period=512.0, first=250.0):
+    """about n T-bars: a jittered lattice; every point within `near_plane` voxels of a z plane
+    `period` apart (the first at z = `first`) was detected a second time within 10 voxels; shuffled"""
+    rs = np.random.RandomState(seed)
+    share = 2 * near_plane / period
+    side = int(round((n / (1 + share)) ** (1 / 3.0)))
+    g = np.arange(side) * spacing + 40.0
+    pts = np.stack(np.meshgrid(g, g, g, indexing='ij'), axis=-1).reshape(-1, 3)
+    pts += rs.randint(-jitter, jitter + 1, pts.shape)
+    to_plane = np.abs((pts[:, 2] - first + period / 2) % period - period / 2)
+    twice = pts[to_plane <= near_plane]
+    pts = np.concatenate([pts, twice + rs.randint(-6, 7, twice.shape)])
+    pts = pts[rs.permutation(len(pts))]
+    conf = (rs.rand(len(pts)) * 0.75 + 0.25).astype(np.float32).astype(np.float64)
+    return {'locs': pts, 'conf': conf}, len(twice)
+
+
+def dedupe_bench(ctx, torch, sizes=(3000, 100000, 1000000), reps=5):
+    """rm_tbar_multi_pred and its neighbour table, host against device"""
+    from flypylib_amd import _nearcapi, fplsynapses, near
+    dev = torch.device('cuda', ctx.device)
+    thresh = 30
+
+    def spread(ms):
+        return dict(median=float(np.median(ms)), min=float(np.min(ms)), max=float(np.max(ms)),
+                    runs=len(ms))
+
+    def timed(fn, k, warm=0):
+        for _ in range(warm):
+            fn()
+        ts, r = [], None
+        for _ in range(k):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize(dev)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return spread(ts), r
+
+    rows = []
+    for n_want in sizes:
+        tb, doubled = dedupe_points(n_want)
+        pts = np.ascontiguousarray(tb['locs'])
+        n = len(pts)
+        row = dict(points=n, doubled=int(doubled), neighbor_thresh=thresh,
+                   timing='wall clock around the call, synchronised; ms; median, min, max')
+        row['table_host_ms'], tab = timed(lambda: near.pairs_numpy(pts, thresh), reps)
+        row['table_device_ms'], tab_d = timed(lambda: near.pairs_device(pts, thresh, ctx.device), reps, warm=2)
+        row['entries'] = int(len(tab[1]))
+        row['longest_row'] = int(np.diff(tab[0]).max())
+        row['equal_tables'] = bool(np.array_equal(tab[0], tab_d[0]) and np.array_equal(tab[1], tab_d[1]))
+        # the steps of pairs_device alone, by HIP events on resident inputs
+        t2 = near.threshold2(thresh)
+        origin, cell, dims = near.grid_of(pts, thresh)
+        stream = torch.cuda.current_stream(dev)
+        p_dev = torch.from_numpy(pts).to(dev)
+        keys0 = torch.empty(n, dtype=torch.int64, device=dev)
+        nscr = _nearcapi.scratch_bytes(n)
+        scratch = torch.empty((nscr + 7) // 8, dtype=torch.int64, device=dev)
+        indices = torch.empty(len(tab[1]), dtype=torch.int32, device=dev)
+        steps = {'keys': [], 'sort': [], 'count_scan': [], 'fill': []}
+        for i in range(2 + reps):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            ev[0].record()
+            _nearcapi.cell_keys(p_dev.data_ptr(), n, origin, cell, dims, keys0.data_ptr(), stream.cuda_stream)
+            ev[1].record()
+            keys, order = torch.sort(keys0)
+            ev[2].record()
+            args = (p_dev.data_ptr(), n, t2, origin, cell, dims, keys.data_ptr(), order.data_ptr(),
+                    scratch.data_ptr(), nscr)
+            total = _nearcapi.pairs_count(*args, stream.cuda_stream)
+            ev[3].record()
+            _nearcapi.pairs_fill(*args, total, indices.data_ptr(), stream.cuda_stream)
+            ev[4].record()
+            torch.cuda.synchronize(dev)
+            if i >= 2:
+                for k, name in enumerate(('keys', 'sort', 'count_scan', 'fill')):
+                    steps[name].append(ev[k].elapsed_time(ev[k + 1]))
+        row['device_steps_ms'] = {k: spread(v) for k, v in steps.items()}
+        row['device_steps_ms']['sum_of_medians'] = float(sum(np.median(v) for v in steps.values()))
+        row['device_steps_timing'] = ('HIP events around each step on resident inputs; count_scan '
+                                      'includes the gather and the read-back of the total')
+        row['device_scratch_bytes'] = int(nscr)
+        del p_dev, keys0, scratch, indices, keys, order
+        # the whole call
+        call_reps = reps
+        row['call_sparse_host_ms'], r_host = timed(
+            lambda: fplsynapses.rm_tbar_multi_pred(tb, neighbor_thresh=thresh, method='sparse'), call_reps)
+        row['call_sparse_device_ms'], r_dev = timed(
+            lambda: fplsynapses.rm_tbar_multi_pred(tb, neighbor_thresh=thresh, method='sparse',
+                                                   device=ctx.device), call_reps)
+        row['equal_results'] = bool(all(np.array_equal(a, b) for a, b in zip(r_host, r_dev)))
+        row['moved'], row['removed'] = int(r_host[1].sum()), int(r_host[0].sum())
+        if n <= 5000:
+            row['call_dense_ms'], r_dense = timed(
+                lambda: fplsynapses.rm_tbar_multi_pred(tb, neighbor_thresh=thresh, method='dense'), reps)
+            row['dense_equals_sparse'] = bool(all(np.array_equal(a, b) for a, b in zip(r_dense, r_host)))
+        else:
+            row['call_dense_ms'] = None
+            row['dense_note'] = 'not run: the distance matrix alone is %.0f GB' % (8.0 * n * n / 1e9)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    return rows
+
+
 def labels_bench(ctx, torch, sizes=(520, 256), reps=5):
     """write_labels_mask, host path against device path"""
     from flypylib_amd import fplsynapses, labels
@@ -516,6 +629,7 @@ def main():
                          "volume in HBM (generated before the clock starts) and cuts the substacks out of it")
     ap.add_argument('--skip-oracle', action='store_true',
                     help='roi: do not re-derive one substack on the CPU oracle (for traces)')
+    ap.add_argument('--dedupe-reps', type=int, default=5)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     import torch
@@ -696,6 +810,11 @@ def main():
         res['match'] = match_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'match.json')
+
+    if 'dedupe' in what:
+        res['dedupe'] = dedupe_bench(ctx, torch, reps=a.dedupe_reps)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'dedupe.json')
 
     if 'labels' in what:
         res['labels'] = labels_bench(ctx, torch)
