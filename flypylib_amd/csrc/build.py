@@ -29,6 +29,11 @@ tables are pinned as they stand; its binding loads lazily, when an evaluation as
 POST_LIBRARIES is a fourth table of that shape, for what runs after the pipeline: libfplnear.so
 finds the close pairs within full_roi_inference's point list, which rm_tbar_multi_pred merges.
 The three tables above are pinned by their tests; its binding loads lazily as well.
+
+SOLVE_LIBRARIES is a fifth table of that shape, beside EVAL_LIBRARIES: libfplassign.so solves
+the matching on the pair table libfplmatch.so leaves on the device (solver='device').  The four
+tables above and ALL_TABLES are pinned by their tests, so its row is a table of its own;
+EVERY_LIBRARY is what build() walks.
 """
 import argparse
 import hashlib
@@ -58,7 +63,11 @@ EVAL_LIBRARIES = (
 POST_LIBRARIES = (
     ('near', 'near', 'fpln', 'fplnear.h', 'libfplnear.so'),            # rm_tbar_multi_pred's close pairs
 )
+SOLVE_LIBRARIES = (
+    ('assign', 'assign', 'fpla', 'fplassign.h', 'libfplassign.so'),    # obj_pr's matching, solved
+)
 ALL_TABLES = SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES + POST_LIBRARIES
+EVERY_LIBRARY = ALL_TABLES + SOLVE_LIBRARIES
 SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
@@ -177,15 +186,16 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in ALL_TABLES:
+    for row in EVERY_LIBRARY:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES or POST_LIBRARIES: same flags,
-    same SHA-stamped rebuild, a version script that exports the row's prefix only"""
-    _, sub, prefix, header, lib = next(r for r in ALL_TABLES if r[0] == key)
+    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES or
+    SOLVE_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the
+    row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in EVERY_LIBRARY if r[0] == key)
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]

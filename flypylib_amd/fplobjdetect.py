@@ -335,6 +335,19 @@ def _sparse_mode(match, device):
     return match == 'sparse' or device is not None
 
 
+SOLVERS = ('host', 'device')
+
+
+def _device_solver(solver, device):
+    """whether the matching is solved by libfplassign.so; the keyword is checked by name"""
+    if solver not in SOLVERS:
+        raise ValueError("solver %r: 'host' (the default) or 'device'" % (solver,))
+    if solver == 'device' and device is None:
+        raise ValueError("solver='device' needs device=<int> or True: the solver runs on the pair "
+                         "table libfplmatch.so leaves on that GPU")
+    return solver == 'device'
+
+
 def _pair_table(predict_locs, groundtruth_locs, dist_thresh, device):
     from . import match as fplmatch
     if device is None:
@@ -352,7 +365,11 @@ def _pr_from_pairs(n_pred, n_gt, i, j, cost, allow_mult):
     from . import match as fplmatch
     if n_pred == 0 or n_gt == 0:
         return _empty_pr(n_pred, n_gt)
-    match = fplmatch.match_sparse(n_pred, n_gt, i, j, cost, allow_mult)
+    return _pr_from_match(n_pred, n_gt, fplmatch.match_sparse(n_pred, n_gt, i, j, cost, allow_mult))
+
+
+def _pr_from_match(n_pred, n_gt, match):
+    """PR_Result of obj_pr from the csr matrix of a sparse matching"""
     num_tp = np.int64(match.nnz)
     per_pred = np.diff(match.indptr).astype(np.int64)
     extra = np.maximum(per_pred - 1, 0).sum()              # predictions matched twice
@@ -361,7 +378,7 @@ def _pr_from_pairs(n_pred, n_gt, i, j, cost, allow_mult):
 
 
 def obj_pr(predict_locs, groundtruth_locs, dist_thresh, predict_lbls=None,
-           groundtruth_lbls=None, allow_mult=False, match='dense', device=None):
+           groundtruth_lbls=None, allow_mult=False, match='dense', device=None, solver='host'):
     """precision / recall of predicted vs ground-truth locations at a distance
     threshold (reference :323-376): pairs closer than `dist_thresh` (and, if labels are
     given, with equal labels) are admissible, `obj_match` picks the matching.
@@ -371,12 +388,23 @@ def obj_pr(predict_locs, groundtruth_locs, dist_thresh, predict_lbls=None,
     and solves the matching per connected component (match.match_sparse): the same optimum
     without the N x M matrix; `match` of the result is then a scipy csr matrix.  device=<int>
     or True (the runtime's default device) implies sparse and takes the pair table from
-    libfplmatch.so's kernels; without torch, a GPU or the library it raises."""
+    libfplmatch.so's kernels; without torch, a GPU or the library it raises.
+
+    solver='host' (default) costs the table in numpy and solves the components with scipy.
+    solver='device' needs `device`: the table stays on the GPU and libfplassign.so costs it,
+    finds the components and solves them there (match.match_device); only the matched pairs
+    are downloaded.  `match` of the result is a csr matrix, as in sparse mode.  Labels must
+    then be integers that fit int64."""
     n_pred, n_gt = predict_locs.shape[0], groundtruth_locs.shape[0]
+    on_device = _device_solver(solver, device)
     if _sparse_mode(match, device):
         from . import match as fplmatch
         if n_pred == 0 or n_gt == 0:
             return _empty_pr(n_pred, n_gt)
+        if on_device:
+            return _pr_from_match(n_pred, n_gt, fplmatch.match_device(
+                predict_locs, groundtruth_locs, dist_thresh, device, predict_lbls, groundtruth_lbls,
+                allow_mult))
         i, j = _pair_table(predict_locs, groundtruth_locs, dist_thresh, device)
         i, j, cost = fplmatch.pair_costs(predict_locs, groundtruth_locs, i, j, dist_thresh,
                                          predict_lbls, groundtruth_lbls)
@@ -397,7 +425,7 @@ def obj_pr(predict_locs, groundtruth_locs, dist_thresh, predict_lbls=None,
 
 
 def _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_lbls,
-                         groundtruth_lbls, allow_mult, device):
+                         groundtruth_lbls, allow_mult, device, on_device=False):
     """obj_pr per confidence threshold from ONE pair table: built over the predictions that
     pass the lowest threshold, then per threshold its rows filtered and renumbered"""
     from . import match as fplmatch
@@ -409,6 +437,13 @@ def _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_
     base = conf >= thresholds.min()
     locs, conf = predict['locs'][base, :], conf[base]
     lbls = None if predict_lbls is None else predict_lbls[base]
+    if on_device:
+        # the table, the costs, the filter per threshold and the matching all stay on the GPU
+        found = fplmatch.match_device(locs, gt_locs, dist_thresh, device, lbls, groundtruth_lbls,
+                                      allow_mult, conf=conf, thresholds=thresholds)
+        # a matrix has a row per selected prediction
+        return [_pr_from_match(m.shape[0], n_gt, m) if m.shape[0] and n_gt else _empty_pr(m.shape[0], n_gt)
+                for m in found]
     if locs.shape[0] and n_gt:
         i, j = _pair_table(locs, gt_locs, dist_thresh, device)
         i, j, cost = fplmatch.pair_costs(locs, gt_locs, i, j, dist_thresh, lbls, groundtruth_lbls)
@@ -427,21 +462,23 @@ def _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_
 
 
 def obj_pr_curve(predict, groundtruth, dist_thresh, thresholds, predict_lbls=None,
-                 groundtruth_lbls=None, allow_mult=False, match='dense', device=None):
+                 groundtruth_lbls=None, allow_mult=False, match='dense', device=None, solver='host'):
     """precision / recall at each confidence threshold (reference :378-436); `predict`
     / `groundtruth` are {'locs','conf'} dicts or json files.
 
-    match / device: as for obj_pr.  In sparse mode the pair table is built once, over the
+    match / device / solver: as for obj_pr.  In sparse mode the pair table is built once, over the
     predictions that pass the lowest threshold, and filtered per threshold; the results are
-    those of obj_pr called per threshold."""
+    those of obj_pr called per threshold.  With solver='device' the one table stays on the GPU
+    for all thresholds."""
     from . import fplsynapses
+    on_device = _device_solver(solver, device)
     if isinstance(predict, str):
         predict = fplsynapses.load_from_json(predict)
     if isinstance(groundtruth, str):
         groundtruth = fplsynapses.load_from_json(groundtruth)
     if _sparse_mode(match, device):
         points = _curve_points_sparse(predict, groundtruth, dist_thresh, thresholds, predict_lbls,
-                                      groundtruth_lbls, allow_mult, device)
+                                      groundtruth_lbls, allow_mult, device, on_device)
     else:
         points = []
         for thd in np.asarray(thresholds).reshape(-1):
@@ -554,7 +591,7 @@ def _gen_volume_host(train_data, context_sz, batch_sz, ratio, rng=None):
 
 def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigma=5,
                        volume_offset=(0, 0, 0), buffer_sz=5, allow_mult=False,
-                       normalize=None, device=None):
+                       normalize=None, device=None, solver='host'):
     """precision / recall curves of a network on labelled substacks (reference
     :463-523): per substack [image, ground-truth json (, segmentation)] -> infer ->
     voxel2obj -> obj_pr_curve against the json's T-bars (buffer applied to both), then
@@ -565,9 +602,12 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
     resident float32 tensor (FplNetwork.infer(device=...)), voxel2obj reads it where it lies
     and obj_pr_curve(device=...) scores the points on the sparse pair table of
     libfplmatch.so; the segmentation lookup stays on the host.  The results equal the host
-    call's.  Without torch, a GPU or the library the call raises."""
+    call's.  Without torch, a GPU or the library the call raises.
+
+    solver: as for obj_pr; 'device' needs `device` and keeps the matching on the GPU as well."""
     from . import fplsynapses
     thds = np.asarray(thds)
+    on_device = _device_solver(solver, device)
     dev = None
     if device is not None:
         from . import match as fplmatch
@@ -592,7 +632,8 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
             lbls_pd, lbls_gt = labels_at(out), labels_at(gt)
         results.append(obj_pr_curve(out, gt, obj_min_dist, thds, lbls_pd, lbls_gt,
                                     allow_mult=allow_mult,
-                                    **({} if dev is None else {'device': dev.index})))
+                                    **({} if dev is None else {'device': dev.index}),
+                                    **({'solver': 'device'} if on_device else {})))
     return aggregate_pr(results), results
 
 

@@ -36,8 +36,8 @@
             fplp_plan_bricks alone (HIP events), the public call from a host and from a
             resident roi_mask, the bytes uploaded; written to profiles/labels.json
   match     obj_pr_curve's matching, all in one process: 3307 x 3000 points in a 520^3 cube at
-            the example script's 18 confidence thresholds - the dense default, match='sparse'
-            and device=... - with the kernels of libfplmatch.so alone (count + scan and fill by
+            the example script's 18 confidence thresholds - the dense default, match='sparse',
+            device=... and device=... with solver='device' - with the kernels of libfplmatch.so alone (count + scan and fill by
             HIP events, each kernel by the profiler where it answers) and the rows downloaded;
             and 10^5 x 10^5 points in a 4096^3 box, sparse host against device only (the dense
             matrix would be 80 GB and is not run); written to profiles/match.json
@@ -347,6 +347,21 @@ def match_bench(ctx, torch, reps=5):
         return all(np.array_equal(getattr(a, f), getattr(b, f))
                    for f in ('num_tp', 'tot_pred', 'tot_gt', 'pp', 'rr'))
 
+    def device_solver(p, g, r_ref, t_dev, k):
+        """solver='device' beside the device= figure of the same process: the whole call, and
+        the stages of one match_device call over all thresholds"""
+        curve(p, g, t_match, thds[-2:], device=ctx.device, solver='device')          # warm-up
+        t_all, r = timed(lambda: curve(p, g, t_match, thds, device=ctx.device, solver='device'), k)
+        base = p['conf'] >= thds.min()
+        info = {}
+        match.match_device(p['locs'][base], g['locs'], t_match, ctx.device, conf=p['conf'][base],
+                           thresholds=thds, info=info)
+        return {'obj_pr_curve_ms': t_all, 'device_over_device_solver': t_dev / t_all,
+                'table_ms': info['table_ms'], 'costs_labels_sort_solve_ms': info['solve_ms'],
+                'download_ms': info['download_ms'], 'overflow': int(sum(info['overflow'])),
+                'sweeps': int(max(info['sweeps'])), 'components': int(max(info['components'])),
+                'largest_component_pairs': int(max(info['largest'])), 'equal_results': bool(same(r, r_ref))}
+
     out = {'thresholds': len(thds), 'dist_thresh': t_match, 'reps': reps}
     # one substack of the example: 3307 predictions, 3000 T-bars in a 520^3 cube
     p, g = points(0, 3000, 2800, 507, 520.0)
@@ -364,6 +379,7 @@ def match_bench(ctx, torch, reps=5):
         'obj_pr_curve_device_ms': t_dev, 'dense_over_sparse': t_dense / t_sparse,
         'dense_over_device': t_dense / t_dev, 'pairs_numpy_ms': t_np, 'pairs_device_ms': t_pd,
         'equal_results': bool(same(r_dense, r_sparse) and same(r_dense, r_dev)),
+        'solver_device': device_solver(p, g, r_dev, t_dev, reps),
         'kernels': kernels(p['locs'], g['locs'])}
     print(json.dumps(out['substack']), flush=True)
     # a whole ROI: 10^5 x 10^5 points in a 4096^3 box
@@ -371,6 +387,8 @@ def match_bench(ctx, torch, reps=5):
     t_pd, tab = timed(lambda: match.pairs_device(p['locs'], g['locs'], t_match, ctx.device), reps)
     t_dev, r_dev = timed(lambda: curve(p, g, t_match, thds, device=ctx.device), 3)
     print('match: roi device %.0f ms' % t_dev, flush=True)
+    roi_solver = device_solver(p, g, r_dev, t_dev, 3)
+    print('match: roi solver=device %s' % json.dumps(roi_solver), flush=True)
     # the host table is two minutes of numpy: built once, inside the curve, and timed there
     host_table = {}
     real = match.pairs_numpy
@@ -394,6 +412,7 @@ def match_bench(ctx, torch, reps=5):
         'sparse_over_device': t_sparse / t_dev, 'pairs_numpy_ms': t_np, 'pairs_device_ms': t_pd,
         'equal_tables': bool(np.array_equal(tab[0], tab_np[0]) and np.array_equal(tab[1], tab_np[1])),
         'equal_results': bool(same(r_sparse, r_dev)),
+        'solver_device': roi_solver,
         'kernels': kernels(p['locs'], g['locs'])}
     print(json.dumps(out['roi']), flush=True)
     return out
