@@ -4,9 +4,12 @@ the pipeline's threshold T = 27 - and the brute-force check that a case has ONE 
 that two correct solvers must return the same matching."""
 import os
 
+import functools
+
 import numpy as np
 
 from flypylib_amd import match
+from flypylib_amd._assigncapi import BLOCK, MAX_BLOCKS, SCAN_THREADS
 from tests import match_cases as cases
 
 T = cases.T
@@ -191,3 +194,242 @@ def assert_unique_optimum(n_pred, i, j, cost, gap=1e-9, limit=8):
         assert second - first > gap, (k, first, second)
         checked += 1
     return checked, skipped
+
+
+def second_best_gap(i, j, cost):
+    """second best total minus best total over all matchings of ONE component's pairs (all of
+    cost < 0), without enumeration.  Any matching other than the optimum lacks at least one pair
+    of the optimum - a strict superset would be cheaper still, every pair costing less than 0 -
+    so the second best is the least of the optima of the problems with one matched pair made
+    absent (cost 0).  One linear_sum_assignment per matched pair."""
+    from scipy.optimize import linear_sum_assignment
+    rows, ri = np.unique(i, return_inverse=True)
+    cols, ci = np.unique(j, return_inverse=True)
+    block = np.zeros((len(rows), len(cols)))
+    block[ri, ci] = cost
+    assert (block[ri, ci] < 0).all()
+    br, bc = linear_sum_assignment(block)
+    optimum = block[br, bc].sum()
+    gap = np.inf
+    for r, c in zip(br, bc):
+        if block[r, c] < 0:
+            kept, block[r, c] = block[r, c], 0.0
+            sr, sc = linear_sum_assignment(block)
+            gap = min(gap, block[sr, sc].sum() - optimum)
+            block[r, c] = kept
+    return gap
+
+
+MIN_GAP = 1e-6      # of a case compared matrix for matrix; the solver's float64 potentials gather
+                    # about 64 roundings of magnitude 27 x 2^-52, about 4e-13
+
+
+def component_gaps(n_pred, i, j, cost):
+    """[(label, distinct rows, distinct columns, pairs, second_best_gap)] of every component, in
+    label order - the order the device solver meets them in; the gap of a single pair is its
+    own cost's magnitude"""
+    i, j, cost = np.asarray(i), np.asarray(j), np.asarray(cost)
+    label = match.components_numpy(n_pred, i, j)
+    out = []
+    for k in np.unique(label):
+        e = label == k
+        out.append((int(k), len(np.unique(i[e])), len(np.unique(j[e])), int(e.sum()),
+                    second_best_gap(i[e], j[e], cost[e])))
+    return out
+
+
+# ---- the ordered compaction ----------------------------------------------------------------------
+# List lengths chosen against the constants of csrc/assign/assign.hip: a block of count_kernel
+# and fill_kernel is one cell of BLOCK entries, scan_kernel's thread t owns the `per` cells from
+# t * per.  tests/test_assign_host.py asserts, without a GPU, that each length is what it says.
+
+def compaction_layout(n):
+    """what the three kernels make of a list of n entries"""
+    cells = -(-n // BLOCK)
+    per = -(-cells // SCAN_THREADS)
+    last_thread = (cells - 1) // per
+    return dict(entries=n, cells=cells, per=per, last_thread=last_thread,
+                last_run=cells - last_thread * per, last_cell=n - (cells - 1) * BLOCK)
+
+
+COMPACTION_SHAPES = {
+    'one': 1, 'wave-1': 63, 'wave': 64, 'wave+1': 65,
+    'cell-1': BLOCK - 1, 'cell': BLOCK, 'cell+1': BLOCK + 1,
+    'scan_full': BLOCK * SCAN_THREADS,
+    'scan_one_over': BLOCK * SCAN_THREADS + 1,
+    'scan_runs_3': BLOCK * (2 * SCAN_THREADS) + BLOCK + 3,
+}
+FLAG_PATTERNS = ('none', 'all', 'first', 'last', 'half', 'every 257th', 'any non-zero')
+INT32_MIN = np.iinfo(np.int32).min
+
+
+def flag_pattern(name, n):
+    rs = np.random.RandomState(n % 9973 + 17 * FLAG_PATTERNS.index(name))
+    flags = np.zeros(n, np.int32)
+    if name == 'all':
+        flags[:] = 1
+    elif name == 'first':
+        flags[0] = 1
+    elif name == 'last':
+        flags[-1] = 1
+    elif name == 'half':
+        flags[:] = rs.rand(n) < 0.5
+        flags[-1] = 1                             # the last cell, and scan run, is never empty
+    elif name == 'every 257th':                   # drifts through the cells, one or none a cell
+        flags[::257] = 1
+    elif name == 'any non-zero':
+        flags[:] = rs.choice(np.array([0, 0, 0, -1, 2, INT32_MIN, 1, 7], np.int32), n)
+        flags[0], flags[n // 2], flags[-1] = -1, 2, INT32_MIN      # (n == 1: the last one holds)
+    return flags
+
+
+@functools.lru_cache(maxsize=None)
+def compaction_columns(n):
+    """(a, b, c): int32, int32 and float64 columns of n entries; c holds NaN of two payloads,
+    -0.0 and infinities, at the list's ends and throughout"""
+    rs = np.random.RandomState(n % 9973)
+    a = rs.randint(INT32_MIN, 2 ** 31 - 1, n).astype(np.int32)
+    b = np.arange(n, dtype=np.int32)[::-1] - 5
+    c = rs.randn(n)
+    special = np.array([np.nan, -0.0, np.inf, -np.inf, 0.0, 5e-324])
+    where = rs.rand(n) < 0.25
+    c[where] = rs.choice(special, int(where.sum()))
+    c[0], c[-1] = np.nan, -0.0
+    other_nan = np.array([0xfff8000000000123], np.uint64).view(np.float64)[0]
+    c[n // 2:n // 2 + 1][np.isnan(c[n // 2:n // 2 + 1])] = other_nan
+    c[n // 3] = other_nan
+    for v in (a, b, c):
+        v.setflags(write=False)
+    return a, b, c
+
+
+def compaction_reference(flags):
+    """(idx, rank): the flagged entries in order, every entry's rank among them or -1"""
+    idx = np.flatnonzero(flags)
+    rank = np.full(len(flags), -1, np.int32)
+    rank[idx] = np.arange(len(idx), dtype=np.int32)
+    return idx.astype(np.int32), rank
+
+
+# ---- beyond one grid stride ------------------------------------------------------------------------
+
+STRIDE = BLOCK * MAX_BLOCKS                     # entries one pass of a grid-stride kernel covers
+STRIDE_SIZES = (STRIDE + 1, 3 * (STRIDE + 1))
+THRESHOLDS = (0.5, float('nan'), float('inf'), float('-inf'))
+
+
+def conf_case(n, thd):
+    """confidences around `thd`: uniform(0, 1) with NaN, both infinities, thd itself and its two
+    float64 neighbours sprinkled throughout and placed at both ends and on both sides of every
+    multiple of STRIDE"""
+    rs = np.random.RandomState(n % 9973)
+    with np.errstate(invalid='ignore'):
+        special = np.array([np.nan, np.inf, -np.inf, thd, np.nextafter(thd, -np.inf),
+                            np.nextafter(thd, np.inf), -0.0, 1.7976931348623157e308])
+    conf = rs.rand(n)
+    where = rs.rand(n) < 0.3
+    conf[where] = rs.choice(special, int(where.sum()))
+    edges = [0, n - len(special)] + [k for k in range(STRIDE - 4, n - len(special), STRIDE)]
+    for e in edges:
+        conf[e:e + len(special)] = special
+    return conf
+
+
+KEY_PATTERNS = ('runs', 'all equal', 'all distinct')
+
+
+def key_case(name, n):
+    """sorted int32 keys: random runs of 1 to 500 entries with a run of one entry at each end and
+    a run across every multiple of STRIDE; one run; n runs"""
+    if name == 'all equal':
+        return np.full(n, 7, np.int32)
+    if name == 'all distinct':
+        return np.arange(n, dtype=np.int32) - 3
+    rs = np.random.RandomState(n % 9973)
+    first = np.zeros(n, bool)
+    at = np.cumsum(rs.randint(1, 501, n // 100))
+    first[at[at < n]] = True
+    for k in range(STRIDE, n, STRIDE):
+        first[k - 2:k + 3] = False
+    first[[1, n - 1]] = True
+    first[n - 2] = False
+    return (np.cumsum(first) * 3 - 1).astype(np.int32)
+
+
+def cube_points(seed, n_pred, n_gt, side, integer):
+    """points uniform in a cube of `side` voxels at C0, integer or fractional"""
+    rs = np.random.RandomState(seed)
+    pred, gt = rs.rand(n_pred, 3) * side + C0, rs.rand(n_gt, 3) * side + C0
+    return (np.rint(pred), np.rint(gt)) if integer else (pred, gt)
+
+
+# name -> (side, integer): 300 x 300 points, the whole cross product as the table.  'full':
+# the cube's diagonal is below T, every row is admissible.  'half': about half of them are.
+COST_CUBES = {'full': (15.0, False), 'full integer': (15.0, True), 'half': (41.0, False),
+              'half integer': (41.0, True)}
+COST_POINTS = 300
+
+
+def cost_table(name):
+    """(pred, gt, i, j): the points of a COST_CUBES case and every pair of them in (i, j) order"""
+    side, integer = COST_CUBES[name]
+    pred, gt = cube_points(11 + len(name), COST_POINTS, COST_POINTS, side, integer)
+    i, j = np.divmod(np.arange(COST_POINTS * COST_POINTS, dtype=np.int32), np.int32(COST_POINTS))
+    return pred, gt, i.astype(np.int32), j.astype(np.int32)
+
+
+# ---- long graphs -----------------------------------------------------------------------------------
+
+def long_chain(k=200, permuted=False):
+    """chain_pairs(k) with the predictions renumbered so that index 0 sits in the middle of the
+    chain and the indices rise towards both ends - every label has half the chain to travel -
+    in (i, j) order, or with the rows in random order"""
+    i, j = chain_pairs(k)
+    i = ((i.astype(np.int64) - k // 2) % k).astype(np.int32)
+    order = np.random.RandomState(k).permutation(len(i)) if permuted else np.lexsort((j, i))
+    return i[order], j[order]
+
+
+# ---- mid-size sparse components ----------------------------------------------------------------------
+
+def rod(seed, n_pred, n_gt, length, integer=False):
+    """(pred, gt) uniform in a length x 8 x 8 rod at 1000: at T = 27 a point pairs with those up
+    to about 27 voxels along the rod, so the component is sparse - many pairs are absent - and
+    its rows and columns come into sight a few per 64 pairs of the table"""
+    rs = np.random.RandomState(seed)
+    pred = rs.rand(n_pred, 3) * [length, 8, 8] + 1000
+    gt = rs.rand(n_gt, 3) * [length, 8, 8] + 1000
+    return (np.rint(pred), np.rint(gt)) if integer else (pred, gt)
+
+
+# (n_pred, n_gt, length, seeds): one component each, one optimum each (test_assign_host.py)
+RODS = [(20, 17, 90, (0, 1, 2)), (17, 20, 90, (0, 1, 2)), (40, 33, 160, (0, 1, 2)),
+        (33, 40, 160, (0, 1, 2)), (64, 64, 300, (0, 1, 2)), (64, 40, 250, (0, 1, 2)),
+        (9, 64, 120, (0, 1, 2)), (64, 9, 120, (0, 1))]
+ROD_CASES = [(seed, n, m, length) for n, m, length, seeds in RODS for seed in seeds]
+TIED_RODS = [(0, 40, 33, 160), (0, 64, 64, 300)]              # integer coordinates: equal costs
+# rods beyond the cap on one side, below CAP * CAP pairs: (seed, n_pred, n_gt, length)
+OVER_THE_CAP_RODS = {'65x20 rod': (0, 65, 20, 200), '20x65 rod': (0, 20, 65, 200)}
+OVER_BY_PAIRS = '65x64'                                        # a full block of 4160 pairs
+
+ROD_SCENE = (('rod', 0, 64, 64, 300), '2x1', ('rod', 0, 9, 64, 120), '3x3 greedy',
+             ('rod', 0, 64, 9, 120), ('rod', 0, 17, 20, 90), '1x1')
+
+
+def scene_of(parts, seed=SOLVE_SEED, shuffle=True):
+    """components - names of component() or ('rod', seed, n_pred, n_gt, length) - 500 voxels
+    apart along y, in this order; the points shuffled as scene() shuffles them, or left in
+    order, so that the components' labels rise in the order given"""
+    rs = np.random.RandomState(seed)
+    built = []
+    for k, part in enumerate(parts):
+        off = np.array([0.0, 500.0 * k, 0.0])
+        if isinstance(part, str):
+            built.append(component(part, seed, C0 + off))
+        else:
+            pred, gt = rod(*part[1:])
+            built.append((pred + off, gt + off))
+    pred, gt = np.concatenate([p for p, _ in built]), np.concatenate([g for _, g in built])
+    if shuffle:
+        pred, gt = pred[rs.permutation(len(pred))], gt[rs.permutation(len(gt))]
+    return pred, gt
