@@ -6,8 +6,7 @@
 //      The admissible rows are then compacted in table order by the three kernels every
 //      stage below shares:
 //        count_kernel   a block counts the flagged entries of its FPLA_BLOCK entries;
-//        scan_kernel    one block scans the per-block counts (uint64 sums, so a total beyond
-//                       int32 is seen, not wrapped);
+//        (scan)         side_scan_kernel of csrc/side/side_device.h over the per-block counts;
 //        fill_kernel    the count again; a flagged entry goes to its block's offset plus its
 //                       rank within the block (ballot + popcount, the waves' sums in LDS).
 //      No atomics: every output has one writer and one place.
@@ -34,10 +33,8 @@
 //                       Every loop has a bound that does not depend on the data's values.
 //   e. the matched flags are compacted (component order, then (i, j)) like any other list.
 //
-// Costs are float64 with every operation rounded on its own: the library is built with
-// -ffp-contract=on, so cost_of() switches contraction off and spells the operations as
-// __dmul_rn / __dadd_rn, as csrc/match/match.hip does; the square root is the correctly
-// rounded one.
+// Costs are float64 with every operation rounded on its own: the squared distance is
+// side_device.h's side_dist2, the square root is the correctly rounded one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +42,7 @@
 
 #include "fplassign.h"
 #include "../side/side_abi.h"
+#include "../side/side_device.h"
 
 // this library's spelling of the shared shell
 #define FPLA_EXPORT SIDE_EXPORT
@@ -55,10 +53,9 @@ namespace {
 
 constexpr int BLOCK = FPLA_BLOCK;
 constexpr int MAX_BLOCKS = FPLA_MAX_BLOCKS;
-constexpr int SCAN_THREADS = FPLA_SCAN_THREADS;
 constexpr int CAP = FPLA_CAP;
 constexpr int WAVE = 64;
-constexpr int64_t LIMIT = 2147483647;
+static_assert(FPLA_SCAN_THREADS == SIDE_SCAN_THREADS, "the scan is side_scan_kernel's block");
 static_assert(CAP == WAVE, "a lane per job");
 static_assert(BLOCK % WAVE == 0 && BLOCK / WAVE <= WAVE, "the waves' sums fit one wave");
 
@@ -92,35 +89,6 @@ __global__ __launch_bounds__(BLOCK) void count_kernel(const int32_t *__restrict_
   uint32_t all;
   block_rank(e < n && flags[e] != 0, wave_sums, &all);
   if (threadIdx.x == 0) cells[blockIdx.x] = all;
-}
-
-// cells[0 .. n) -> exclusive offsets in place (mod 2^32: only a total within int32 is used),
-// *total = their sum
-__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(uint32_t *__restrict__ cells,
-                                                            uint32_t n,
-                                                            unsigned long long *__restrict__ total) {
-  __shared__ unsigned long long sums[SCAN_THREADS];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-  const uint32_t lo = (uint32_t)std::min<uint64_t>((uint64_t)t * per, n);
-  const uint32_t hi = (uint32_t)std::min<uint64_t>((uint64_t)lo + per, n);
-  unsigned long long own = 0;
-  for (uint32_t j = lo; j < hi; ++j) own += cells[j];
-  sums[t] = own;
-  __syncthreads();
-  for (uint32_t off = 1; off < SCAN_THREADS; off <<= 1) {
-    const unsigned long long v = t >= off ? sums[t - off] : 0ull;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = (uint32_t)(sums[t] - own);
-  for (uint32_t j = lo; j < hi; ++j) {
-    const uint32_t v = cells[j];
-    cells[j] = run;
-    run += v;
-  }
-  if (t == SCAN_THREADS - 1) *total = sums[t];
 }
 
 struct Fill {
@@ -175,10 +143,8 @@ struct Costs {
 };
 
 __device__ __forceinline__ double cost_of(const double *p, const double *g, double t) {
-#pragma clang fp contract(off)
-  const double dx = p[0] - g[0], dy = p[1] - g[1], dz = p[2] - g[2];
-  const double s = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-  return __builtin_sqrt(s) - t;           // llvm.sqrt.f64: IEEE, correctly rounded
+  // llvm.sqrt.f64: IEEE, correctly rounded
+  return __builtin_sqrt(side_dist2(p[0], p[1], p[2], g[0], g[1], g[2])) - t;
 }
 
 __global__ __launch_bounds__(BLOCK) void cost_kernel(Costs a, int32_t *__restrict__ i_out,
@@ -411,11 +377,7 @@ __global__ __launch_bounds__(WAVE) void solve_kernel(const int32_t *__restrict__
 
 // ---- argument checks --------------------------------------------------------------------------
 
-int count_ok(const char *fn, const char *what, int64_t n) {
-  if (n < 1 || n > LIMIT)
-    return fpla_fail("%s: %s %lld must lie in [1, 2^31 - 1]", fn, what, (long long)n);
-  return 0;
-}
+int count_ok(const char *fn, const char *what, int64_t n) { return in_int32_range(fn, what, n, 1); }
 
 int scratch_ok(const char *fn, const void *scratch, int64_t scratch_bytes, int64_t n) {
   if (!aligned(scratch, 8) || scratch_bytes < scratch_for(n))
@@ -455,14 +417,11 @@ FPLA_EXPORT int fpla_flags_count(const int32_t *flags, int64_t n, void *scratch,
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(count_kernel, dim3((unsigned)blocks_of(n)), dim3(BLOCK), 0, st, flags, n, cells);
   if (launched("fpla_flags_count")) return 1;
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, cells, (uint32_t)blocks_of(n),
-                     sum);
+  hipLaunchKernelGGL(side_scan_kernel<uint32_t>, dim3(1), dim3(SIDE_SCAN_THREADS), 0, st, cells,
+                     (uint32_t)blocks_of(n), sum, nullptr);
   if (launched("fpla_flags_count (scan)")) return 1;
   unsigned long long got = 0;
-  hipError_t e = hipMemcpyAsync(&got, sum, sizeof(got), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    return fpla_fail("%s: reading the total failed: %s", fn, hipGetErrorString(e));
+  if (side_read_back(fn, st, &got, sum, sizeof(got))) return 1;
   *total = (int64_t)got;                    // at most n
   return 0;
 } FPLA_CATCH()
@@ -475,8 +434,7 @@ FPLA_EXPORT int fpla_flags_fill(const int32_t *flags, int64_t n, const void *scr
   const char *fn = "fpla_flags_fill";
   if (!flags || !scratch) return fpla_fail("%s: null pointer argument", fn);
   if (count_ok(fn, "n", n)) return 1;
-  if (capacity < 0 || capacity > LIMIT)
-    return fpla_fail("%s: capacity %lld must lie in [0, 2^31 - 1]", fn, (long long)capacity);
+  if (in_int32_range(fn, "capacity", capacity, 0)) return 1;
   if ((a_out && !a) || (b_out && !b) || (c_out && !c))
     return fpla_fail("%s: an output column without its input column", fn);
   if (!aligned(flags, 4) || !aligned(a, 4) || !aligned(b, 4) || !aligned(a_out, 4) ||

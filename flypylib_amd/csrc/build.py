@@ -13,8 +13,8 @@ runs in the CPU-only build container.
 Every row of SIDE_LIBRARIES is a library of its own: its sources live in a directory under
 csrc/, are compiled with the same flags and stamps, and its version script exports its own
 prefix only - libfplhip.so's export list stays the fpl_* names of include/fplhip.h.  The
-side libraries share the C shell of csrc/side/side_abi.h, which is part of their stamps and
-not of libfplhip.so's.
+side libraries share the headers of csrc/side/ (the C shell of side_abi.h, the device code of
+side_device.h), which are part of their stamps and not of libfplhip.so's.
 
 STAGE_LIBRARIES holds rows of the same shape, built in the same way: libraries that serve a
 stage of a side library rather than a device stage of their own (libfplplan.so plans the
@@ -68,7 +68,6 @@ SOLVE_LIBRARIES = (
 )
 ALL_TABLES = SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES + POST_LIBRARIES
 EVERY_LIBRARY = ALL_TABLES + SOLVE_LIBRARIES
-SIDE_ABI = os.path.join(HERE, 'side', 'side_abi.h')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -200,7 +199,9 @@ def build_side(key, force=False, jobs=4, verbose=True):
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]
     return _build_library(os.path.join(LIB_DIR, lib), prefix + '_*', srcs, src_dir,
-                          _digest(_local_headers(src_dir) + [SIDE_ABI, os.path.join(inc, header)]),
+                          _digest(_local_headers(src_dir)
+                                  + _local_headers(os.path.join(HERE, 'side'))
+                                  + [os.path.join(inc, header)]),
                           force, jobs, verbose)
 
 

@@ -196,7 +196,6 @@ FPLL_EXPORT int fpll_labels_mask(const uint8_t *roi, const int32_t *tbars, int64
   for (int a = 0; a < 3; ++a)
     if (dims[a] < 1) return fpll_fail("%s: dims (%lld,%lld,%lld) must be positive", fn,
                                       (long long)dims[0], (long long)dims[1], (long long)dims[2]);
-  const int64_t lim = 2147483647;
   int64_t voxels;
   if (volume_voxels(fn, dims, "the brick tables", "render it in parts", &voxels)) return 1;
   if (radius_use < 0 || radius_ign < 0 || radius_use > FPLL_MAX_RADIUS ||
@@ -204,7 +203,7 @@ FPLL_EXPORT int fpll_labels_mask(const uint8_t *roi, const int32_t *tbars, int64
     return fpll_fail("%s: radius_use %d / radius_ign %d must lie in [0, %d]", fn, radius_use,
                      radius_ign, FPLL_MAX_RADIUS);
   if (buffer_size < 0) return fpll_fail("%s: buffer_size %d must not be negative", fn, buffer_size);
-  if (n_tbars < 0 || n_tbars > lim / 3 || n_index < 0 || n_index > lim)
+  if (n_tbars < 0 || n_tbars > SIDE_INT32_MAX / 3 || n_index < 0 || n_index > SIDE_INT32_MAX)
     return fpll_fail("%s: n_tbars %lld / n_index %lld", fn, (long long)n_tbars, (long long)n_index);
   if (n_index > 0 && (!tbars || !brick_offsets || !brick_index || n_tbars == 0))
     return fpll_fail("%s: null pointer argument (a table of %lld candidates)", fn,
@@ -224,9 +223,10 @@ FPLL_EXPORT int fpll_labels_mask(const uint8_t *roi, const int32_t *tbars, int64
   g.nb1 = (int)((dims[1] + BY - 1) / BY);
   g.nb2 = (int)((dims[2] + BX - 1) / BX);
   const int64_t bricks = nb0 * g.nb1 * g.nb2;
-  if (bricks > lim) return fpll_fail("%s: %lld bricks exceed a grid", fn, (long long)bricks);
+  if (bricks > SIDE_INT32_MAX)
+    return fpll_fail("%s: %lld bricks exceed a grid", fn, (long long)bricks);
   // buffer_size 0 clears everything (mask[-0:] = 0 on the host), as does one beyond an extent
-  const int64_t b = buffer_size == 0 ? lim : buffer_size;
+  const int64_t b = buffer_size == 0 ? SIDE_INT32_MAX : buffer_size;
   g.b0 = (int)(b > dims[0] ? dims[0] : b);
   g.b1 = (int)(b > dims[1] ? dims[1] : b);
   g.b2 = (int)(b > dims[2] ? dims[2] : b);

@@ -11,17 +11,12 @@
 //                 same address, a broadcast read without bank conflicts - and tests it.  One
 //                 uint32 per (prediction, segment) cell, prediction-major; an empty segment
 //                 writes its zeros.
-//   scan_kernel   one block of FPLE_SCAN_THREADS threads: each thread sums a run of
-//                 consecutive cells, the sums (uint64) are scanned in LDS, each thread rewrites
-//                 its run as exclusive offsets; the total is kept as a uint64 in front of the
-//                 cells, so a table beyond int32 rows is seen and refused, not wrapped.
+//   (scan)        side_scan_kernel of csrc/side/side_device.h; the uint64 total sits in front.
 //   fill_kernel   the count pass again; a thread writes its rows from its cell's offset in
 //                 ascending j.  Cells are prediction-major and segments ascend in j, so the
 //                 table is in (i, j) order whatever order the blocks run in.  No atomics.
 //
-// s = (dx * dx + dy * dy) + dz * dz with every operation rounded on its own: the library is
-// built with -ffp-contract=on, so dist2() switches contraction off and spells the operations
-// as __dmul_rn / __dadd_rn.  That is numpy's (delta ** 2).sum(axis=2), bit for bit.
+// The squared distance is side_device.h's side_dist2: numpy's (delta ** 2).sum(axis=2) to the bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +24,7 @@
 
 #include "fplmatch.h"
 #include "../side/side_abi.h"
+#include "../side/side_device.h"
 
 // this library's spelling of the shared shell
 #define FPLE_EXPORT SIDE_EXPORT
@@ -39,8 +35,7 @@ namespace {
 
 constexpr int BLOCK = FPLE_BLOCK;
 constexpr int TILE = FPLE_TILE;
-constexpr int SCAN_THREADS = FPLE_SCAN_THREADS;
-constexpr int64_t LIMIT = 2147483647;
+static_assert(FPLE_SCAN_THREADS == SIDE_SCAN_THREADS, "the scan is side_scan_kernel's block");
 static_assert(TILE == BLOCK, "a thread loads three doubles of a tile");
 
 struct Points {
@@ -50,13 +45,6 @@ struct Points {
   uint32_t seg_len;             // ground-truth points per segment, whole tiles
   double T2;
 };
-
-__device__ __forceinline__ double dist2(double px, double py, double pz, double gx, double gy,
-                                        double gz) {
-#pragma clang fp contract(off)
-  const double dx = px - gx, dy = py - gy, dz = pz - gz;
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
 
 // the pairs of prediction i within segment blockIdx.y: counted, and with FILL written from `row`
 template <bool FILL>
@@ -85,7 +73,7 @@ __device__ __forceinline__ uint32_t walk_segment(const Points &p, double *tile, 
     }
     __syncthreads();
     for (uint32_t k = 0; k < n; ++k) {
-      const double s = dist2(px, py, pz, tile[3 * k], tile[3 * k + 1], tile[3 * k + 2]);
+      const double s = side_dist2(px, py, pz, tile[3 * k], tile[3 * k + 1], tile[3 * k + 2]);
       if (live && s <= p.T2) {
         if (FILL) {
           if (row < capacity) {
@@ -108,35 +96,6 @@ __global__ __launch_bounds__(BLOCK) void count_kernel(Points p, uint32_t *__rest
   if (i < p.n_pred) cells[(size_t)i * p.segments + blockIdx.y] = count;
 }
 
-// cells[0 .. n) -> exclusive offsets in place (mod 2^32: only a total within int32 rows is
-// used), *total = their sum
-__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(uint32_t *__restrict__ cells,
-                                                            uint32_t n,
-                                                            unsigned long long *__restrict__ total) {
-  __shared__ unsigned long long sums[SCAN_THREADS];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-  const uint32_t lo = (uint32_t)std::min<uint64_t>((uint64_t)t * per, n);
-  const uint32_t hi = (uint32_t)std::min<uint64_t>((uint64_t)lo + per, n);
-  unsigned long long own = 0;
-  for (uint32_t j = lo; j < hi; ++j) own += cells[j];
-  sums[t] = own;
-  __syncthreads();
-  for (uint32_t off = 1; off < SCAN_THREADS; off <<= 1) {
-    const unsigned long long v = t >= off ? sums[t - off] : 0ull;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = (uint32_t)(sums[t] - own);
-  for (uint32_t j = lo; j < hi; ++j) {
-    const uint32_t v = cells[j];
-    cells[j] = run;
-    run += v;
-  }
-  if (t == SCAN_THREADS - 1) *total = sums[t];
-}
-
 __global__ __launch_bounds__(BLOCK) void fill_kernel(Points p, const uint32_t *__restrict__ offsets,
                                                      uint32_t capacity, int32_t *__restrict__ i_out,
                                                      int32_t *__restrict__ j_out) {
@@ -156,13 +115,10 @@ uint32_t segments_of(int64_t n_pred, int64_t n_gt) {
 }
 
 int counts_ok(const char *fn, int64_t n_pred, int64_t n_gt) {
-  if (n_pred < 1 || n_pred > LIMIT)
-    return fple_fail("%s: n_pred %lld must lie in [1, 2^31 - 1]", fn, (long long)n_pred);
-  if (n_gt < 1 || n_gt > LIMIT)
-    return fple_fail("%s: n_gt %lld must lie in [1, 2^31 - 1]", fn, (long long)n_gt);
+  if (in_int32_range(fn, "n_pred", n_pred, 1) || in_int32_range(fn, "n_gt", n_gt, 1)) return 1;
   // more than FPLE_TARGET_BLOCKS blocks of predictions are one segment, so this holds for
   // every n_pred: 2^31 - 1 cells at the most
-  if (n_pred * (int64_t)segments_of(n_pred, n_gt) > LIMIT)
+  if (n_pred * (int64_t)segments_of(n_pred, n_gt) > SIDE_INT32_MAX)
     return fple_fail("%s: %lld predictions in %u segments exceed 2^31 - 1 cells", fn,
                      (long long)n_pred, segments_of(n_pred, n_gt));
   return 0;
@@ -225,15 +181,12 @@ FPLE_EXPORT int fple_pairs_count(const double *pred, int64_t n_pred, const doubl
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(count_kernel, grid_of(p), dim3(BLOCK), 0, st, p, cells);
   if (launched("fple_pairs_count")) return 1;
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, cells,
-                     p.n_pred * p.segments, sum);
+  hipLaunchKernelGGL(side_scan_kernel<uint32_t>, dim3(1), dim3(SIDE_SCAN_THREADS), 0, st, cells,
+                     p.n_pred * p.segments, sum, nullptr);
   if (launched("fple_pairs_count (scan)")) return 1;
   unsigned long long got = 0;
-  hipError_t e = hipMemcpyAsync(&got, sum, sizeof(got), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    return fple_fail("%s: reading the total failed: %s", fn, hipGetErrorString(e));
-  if (got > (unsigned long long)LIMIT)
+  if (side_read_back(fn, st, &got, sum, sizeof(got))) return 1;
+  if (got > (unsigned long long)SIDE_INT32_MAX)
     return fple_fail("%s: %llu pairs exceed the 2^31 - 1 rows of an int32 table; match the points "
                      "in parts", fn, got);
   *total = (int64_t)got;
@@ -247,8 +200,7 @@ FPLE_EXPORT int fple_pairs_fill(const double *pred, int64_t n_pred, const double
   const char *fn = "fple_pairs_fill";
   Points p;
   if (pair_args(fn, pred, n_pred, gt, n_gt, T2, scratch, scratch_bytes, &p)) return 1;
-  if (capacity < 0 || capacity > LIMIT)
-    return fple_fail("%s: capacity %lld must lie in [0, 2^31 - 1]", fn, (long long)capacity);
+  if (in_int32_range(fn, "capacity", capacity, 0)) return 1;
   if (capacity == 0) return 0;
   if (!i_out || !j_out) return fple_fail("%s: null pointer argument (an output column)", fn);
   if (!aligned(i_out, 4) || !aligned(j_out, 4))

@@ -16,9 +16,8 @@
 //   count_kernel  one wave per chunk of FPLM_CHUNK flat voxels, 16 steps of 64 lanes x 4
 //                 voxels; per step four ballots (one per voxel of the lane) and their
 //                 popcounts; lane 0 stores the chunk's count.
-//   scan_kernel   one block of 1024 threads: each thread sums a run of consecutive
-//                 counts, the 1024 sums are scanned in LDS, each thread rewrites its run
-//                 as exclusive offsets; the total lands behind the last chunk.
+//   (scan)        side_scan_kernel of csrc/side/side_device.h; the total lands behind the
+//                 last chunk.
 //   fill_kernel   the count pass again; a row's place is its chunk's offset + the rows of
 //                 the steps before + the set ballot bits of lower lanes + the lane's own
 //                 earlier voxels: C order, whatever order the waves run in.
@@ -31,6 +30,7 @@
 
 #include "fplmine.h"
 #include "../side/side_abi.h"
+#include "../side/side_device.h"
 
 // this library's spelling of the shared shell
 #define FPLM_EXPORT SIDE_EXPORT
@@ -44,6 +44,7 @@ constexpr int LANE_VOX = 4;                // voxels per lane and step
 constexpr int STEP = 64 * LANE_VOX;        // voxels per wave and step
 constexpr int STEPS = FPLM_CHUNK / STEP;   // steps per chunk
 constexpr int SCAN_THREADS = 1024;
+static_assert(SCAN_THREADS == SIDE_SCAN_THREADS, "the scan is side_scan_kernel's block");
 static_assert(FPLM_CHUNK % STEP == 0, "a chunk is a whole number of wave steps");
 
 struct Geometry {
@@ -194,32 +195,6 @@ __global__ __launch_bounds__(BLOCK) void count_kernel(Candidates c, Geometry g, 
   if (lane == 0) counts[chunk] = count;
 }
 
-// counts[0 .. n_chunks) -> exclusive offsets in place, counts[n_chunks] = total
-__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(uint32_t *__restrict__ counts,
-                                                            uint32_t n_chunks) {
-  __shared__ uint32_t sums[SCAN_THREADS];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (n_chunks + SCAN_THREADS - 1) / SCAN_THREADS;
-  const uint32_t lo = min(t * per, n_chunks), hi = min(lo + per, n_chunks);
-  uint32_t own = 0;
-  for (uint32_t j = lo; j < hi; ++j) own += counts[j];
-  sums[t] = own;
-  __syncthreads();
-  for (uint32_t off = 1; off < SCAN_THREADS; off <<= 1) {
-    const uint32_t v = t >= off ? sums[t - off] : 0u;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = sums[t] - own;
-  for (uint32_t j = lo; j < hi; ++j) {
-    const uint32_t v = counts[j];
-    counts[j] = run;
-    run += v;
-  }
-  if (t == SCAN_THREADS - 1) counts[n_chunks] = sums[t];
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(BLOCK) void fill_kernel(Candidates c, Geometry g, uint32_t n_chunks,
                                                      const uint32_t *__restrict__ offsets,
@@ -360,13 +335,11 @@ FPLM_EXPORT int fplm_candidates_count(const uint8_t *labels, const uint8_t *mask
   else
     hipLaunchKernelGGL(count_kernel<false>, grid, dim3(BLOCK), 0, st, c, g, n_chunks, counts);
   if (launched("fplm_candidates_count")) return 1;
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, counts, n_chunks);
+  hipLaunchKernelGGL(side_scan_kernel<uint32_t>, dim3(1), dim3(SCAN_THREADS), 0, st, counts,
+                     n_chunks, nullptr, counts + n_chunks);
   if (launched("fplm_candidates_count (scan)")) return 1;
   uint32_t got = 0;
-  hipError_t e = hipMemcpyAsync(&got, counts + n_chunks, sizeof(got), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    return fplm_fail("fplm_candidates_count: reading the total failed: %s", hipGetErrorString(e));
+  if (side_read_back("fplm_candidates_count", st, &got, counts + n_chunks, sizeof(got))) return 1;
   *total = (int64_t)got;
   return 0;
 } FPLM_CATCH()
@@ -383,7 +356,7 @@ FPLM_EXPORT int fplm_candidates_fill(const uint8_t *labels, const uint8_t *mask,
   if (candidate_args("fplm_candidates_fill", labels, mask, weights, dims, half, cc, scratch,
                      scratch_bytes, &c, &g, &vec))
     return 1;
-  if (capacity < 0 || capacity > 2147483647)
+  if (capacity < 0 || capacity > SIDE_INT32_MAX)
     return fplm_fail("fplm_candidates_fill: capacity %lld", (long long)capacity);
   if (capacity == 0) return 0;
   if (!z_out || !y_out || !x_out || (weights && !w_out))

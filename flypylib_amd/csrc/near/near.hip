@@ -17,10 +17,8 @@
 //                  column per thread (the loops over them are not unrolled, so in registers they
 //                  would be indexed dynamically and go to scratch).  Every candidate is tested;
 //                  the count goes to the point's ORIGINAL index.
-//   scan_kernel    one block of FPLN_SCAN_THREADS threads: each thread sums a run of consecutive
-//                  counts, the sums (uint64) are scanned in LDS, each thread rewrites its run as
-//                  exclusive offsets; the total is kept as a uint64 in front, so a table beyond
-//                  int32 entries is seen and refused, not wrapped.
+//   (scan)         side_scan_kernel of csrc/side/side_device.h; the total as a uint64 in front
+//                  and as the last of the n + 1 row offsets.
 //   fill_kernel    the count pass again.  The candidates come in cell order, not in ascending j,
 //                  and a row may be longer than any per-thread buffer, so a partner is placed by
 //                  rank: it goes to the row's offset plus the number of the row's partners with a
@@ -30,9 +28,7 @@
 //                  buffer, no second table and no atomics: every entry has one writer and one
 //                  place, whatever order the blocks run in.
 //
-// s = (dx * dx + dy * dy) + dz * dz with every operation rounded on its own: the library is
-// built with -ffp-contract=on, so dist2() switches contraction off and spells the operations
-// as __dmul_rn / __dadd_rn, as csrc/match/match.hip does.
+// The squared distance is side_device.h's side_dist2, every operation rounded on its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +36,7 @@
 
 #include "fplnear.h"
 #include "../side/side_abi.h"
+#include "../side/side_device.h"
 
 // this library's spelling of the shared shell
 #define FPLN_EXPORT SIDE_EXPORT
@@ -49,8 +46,7 @@
 namespace {
 
 constexpr int BLOCK = FPLN_BLOCK;
-constexpr int SCAN_THREADS = FPLN_SCAN_THREADS;
-constexpr int64_t LIMIT = 2147483647;
+static_assert(FPLN_SCAN_THREADS == SIDE_SCAN_THREADS, "the scan is side_scan_kernel's block");
 constexpr int64_t MAX_AXIS = (int64_t)1 << FPLN_MAX_AXIS_BITS;
 constexpr int RUNS = 9;                     // the (dy, dz) neighbours of a cell row
 
@@ -97,13 +93,6 @@ __device__ __forceinline__ int64_t cell_of(double x, double o, double cell, int6
   double u = (x - o) / cell;
   u = fmin(fmax(u, 0.0), (double)(n - 1));  // a NaN reads as 0
   return (int64_t)floor(u);
-}
-
-__device__ __forceinline__ double dist2(double px, double py, double pz, double gx, double gy,
-                                        double gz) {
-#pragma clang fp contract(off)
-  const double dx = px - gx, dy = py - gy, dz = pz - gz;
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
 __global__ __launch_bounds__(BLOCK) void keys_kernel(const double *__restrict__ locs, uint32_t n,
@@ -169,7 +158,7 @@ __device__ __forceinline__ void find_runs(const Near &a, double px, double py, d
 
 __device__ __forceinline__ bool partner(const Near &a, double px, double py, double pz, uint32_t q) {
   const double *c = a.pts + (size_t)q * 3;
-  const double s = dist2(px, py, pz, c[0], c[1], c[2]);
+  const double s = side_dist2(px, py, pz, c[0], c[1], c[2]);
   return s > 0.0 && s <= a.T2;
 }
 
@@ -188,38 +177,6 @@ __global__ __launch_bounds__(BLOCK) void count_kernel(Near a, uint32_t *__restri
       count += partner(a, px, py, pz, q) ? 1u : 0u;
   }
   counts[a.perm[k]] = count;
-}
-
-// cells[0 .. n) -> exclusive offsets in place (mod 2^32: only a total within int32 entries is
-// used), cells[n] and *total = their sum
-__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(uint32_t *__restrict__ cells,
-                                                            uint32_t n,
-                                                            unsigned long long *__restrict__ total) {
-  __shared__ unsigned long long sums[SCAN_THREADS];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-  const uint32_t lo = (uint32_t)std::min<uint64_t>((uint64_t)t * per, n);
-  const uint32_t hi = (uint32_t)std::min<uint64_t>((uint64_t)lo + per, n);
-  unsigned long long own = 0;
-  for (uint32_t j = lo; j < hi; ++j) own += cells[j];
-  sums[t] = own;
-  __syncthreads();
-  for (uint32_t off = 1; off < SCAN_THREADS; off <<= 1) {
-    const unsigned long long v = t >= off ? sums[t - off] : 0ull;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = (uint32_t)(sums[t] - own);
-  for (uint32_t j = lo; j < hi; ++j) {
-    const uint32_t v = cells[j];
-    cells[j] = run;
-    run += v;
-  }
-  if (t == SCAN_THREADS - 1) {
-    cells[n] = (uint32_t)sums[t];
-    *total = sums[t];
-  }
 }
 
 __global__ __launch_bounds__(BLOCK) void fill_kernel(Near a, const uint32_t *__restrict__ offsets,
@@ -251,10 +208,7 @@ __global__ __launch_bounds__(BLOCK) void fill_kernel(Near a, const uint32_t *__r
   }
 }
 
-int count_ok(const char *fn, int64_t n) {
-  if (n < 1 || n > LIMIT) return fpln_fail("%s: n %lld must lie in [1, 2^31 - 1]", fn, (long long)n);
-  return 0;
-}
+int count_ok(const char *fn, int64_t n) { return in_int32_range(fn, "n", n, 1); }
 
 int grid_args(const char *fn, const double *origin, double cell, const int64_t *dims, Grid *g) {
   if (!origin || !dims) return fpln_fail("%s: null pointer argument (the grid)", fn);
@@ -355,16 +309,14 @@ FPLN_EXPORT int fpln_pairs_count(const double *locs, int64_t n, double T2, const
   if (launched("fpln_pairs_count (gather)")) return 1;
   hipLaunchKernelGGL(count_kernel, grid_of(n), dim3(BLOCK), 0, st, a, s.offsets);
   if (launched("fpln_pairs_count")) return 1;
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, s.offsets, a.n, s.total);
+  hipLaunchKernelGGL(side_scan_kernel<uint32_t>, dim3(1), dim3(SIDE_SCAN_THREADS), 0, st, s.offsets,
+                     a.n, s.total, s.offsets + a.n);
   if (launched("fpln_pairs_count (scan)")) return 1;
   unsigned long long head[2] = {0, 0};      // the total, the status word
-  e = hipMemcpyAsync(head, scratch, sizeof(head), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    return fpln_fail("%s: reading the total failed: %s", fn, hipGetErrorString(e));
+  if (side_read_back(fn, st, head, scratch, sizeof(head))) return 1;
   if ((uint32_t)head[1] != 0)
     return fpln_fail("%s: an entry of the order lies outside [0, %lld)", fn, (long long)n);
-  if (head[0] > (unsigned long long)LIMIT)
+  if (head[0] > (unsigned long long)SIDE_INT32_MAX)
     return fpln_fail("%s: %llu table entries exceed the 2^31 - 1 of an int32 table; merge the "
                      "points in parts", fn, head[0]);
   *total = (int64_t)head[0];
@@ -379,8 +331,7 @@ FPLN_EXPORT int fpln_pairs_fill(const double *locs, int64_t n, double T2, const 
   Near a;
   if (pair_args(fn, locs, n, T2, origin, cell, dims, sorted_keys, order, scratch, scratch_bytes, &a))
     return 1;
-  if (capacity < 0 || capacity > LIMIT)
-    return fpln_fail("%s: capacity %lld must lie in [0, 2^31 - 1]", fn, (long long)capacity);
+  if (in_int32_range(fn, "capacity", capacity, 0)) return 1;
   if (capacity == 0) return 0;
   if (!indices) return fpln_fail("%s: null pointer argument (the column array)", fn);
   if (!aligned(indices, 4)) return fpln_fail("%s: the column array is not 4-byte aligned", fn);

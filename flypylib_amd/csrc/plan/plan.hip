@@ -7,9 +7,9 @@
 //   count_kernel      one wave per T-bar: its lanes walk the T-bar's clamped brick range and
 //                     add 1 to each brick's counter
 //   tile_sum_kernel   a block of 1024 threads per tile of 1024 counters: the tile's sum
-//   tile_scan_kernel  one block: exclusive scan of the tile sums (a run of tiles per thread,
-//                     the 1024 run sums scanned in LDS); the total goes behind the last brick
-//                     and is compared with n_index for the status word
+//   tile_scan_kernel  one block: side_scan_runs of csrc/side/side_device.h over the tile sums;
+//                     the total goes behind the last brick and is compared with n_index for
+//                     the status word
 //   offsets_kernel    per tile: exclusive scan of its counters in LDS plus the tile's prefix,
 //                     written over the counters
 //   fill_kernel       the count pass again; a pair's place in the staging list is its brick's
@@ -32,6 +32,7 @@
 #include "fpllabels.h"
 #include "fplplan.h"
 #include "../side/side_abi.h"
+#include "../side/side_device.h"
 
 // this library's spelling of the shared shell
 #define FPLP_EXPORT SIDE_EXPORT
@@ -47,10 +48,10 @@ namespace {
 constexpr int BLOCK = 256;                 // 4 waves
 constexpr int WAVE = 64;
 constexpr int TILE = 1024;                 // counters per scan block, one per thread
+static_assert(TILE == SIDE_SCAN_THREADS, "a tile is side_block_scan's block");
 constexpr unsigned MAX_BLOCKS = 1u << 16;  // of BLOCK threads; more work goes by stride
 constexpr unsigned MAX_TILE_BLOCKS = 1u << 13;
 constexpr int BZ = FPLP_BRICK_Z, BY = FPLP_BRICK_Y, BX = FPLP_BRICK_X;
-typedef unsigned long long u64;
 
 struct Plan {
   int nb0, nb1, nb2;        // bricks along z, y, x
@@ -109,27 +110,13 @@ __global__ __launch_bounds__(BLOCK) void count_kernel(const int32_t *__restrict_
   }
 }
 
-// inclusive scan of one value per thread over a block of TILE threads
-__device__ __forceinline__ u64 block_scan(u64 own, u64 *sums) {
-  const unsigned t = threadIdx.x;
-  sums[t] = own;
-  __syncthreads();
-  for (unsigned off = 1; off < (unsigned)TILE; off <<= 1) {
-    const u64 v = t >= off ? sums[t - off] : 0ull;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  return sums[t];
-}
-
 __global__ __launch_bounds__(TILE) void tile_sum_kernel(const int32_t *__restrict__ counts,
                                                         unsigned n_bricks, unsigned tiles,
                                                         u64 *__restrict__ tile_sums) {
   __shared__ u64 sums[TILE];
   for (unsigned tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const unsigned i = tile * (unsigned)TILE + threadIdx.x;
-    const u64 incl = block_scan(i < n_bricks ? (u64)(unsigned)counts[i] : 0ull, sums);
+    const u64 incl = side_block_scan(i < n_bricks ? (u64)(unsigned)counts[i] : 0ull, sums);
     if (threadIdx.x == TILE - 1) tile_sums[tile] = incl;
   }
 }
@@ -142,21 +129,10 @@ __global__ __launch_bounds__(TILE) void tile_scan_kernel(u64 *__restrict__ tile_
                                                          unsigned n_bricks, unsigned n_index,
                                                          int32_t *__restrict__ status) {
   __shared__ u64 sums[TILE];
-  const unsigned t = threadIdx.x;
-  const unsigned per = (tiles + TILE - 1) / TILE;
-  const unsigned lo = min(t * per, tiles), hi = min(lo + per, tiles);
-  u64 own = 0;
-  for (unsigned j = lo; j < hi; ++j) own += tile_sums[j];
-  const u64 incl = block_scan(own, sums);
-  u64 run = incl - own;
-  for (unsigned j = lo; j < hi; ++j) {
-    const u64 v = tile_sums[j];
-    tile_sums[j] = run;
-    run += v;
-  }
-  if (t == TILE - 1) {
-    offsets[n_bricks] = (int32_t)incl;
-    *status = incl != (u64)n_index ? 1 : 0;
+  const u64 total = side_scan_runs<u64>(tile_sums, tiles, sums);
+  if (threadIdx.x == TILE - 1) {
+    offsets[n_bricks] = (int32_t)total;
+    *status = total != (u64)n_index ? 1 : 0;
   }
 }
 
@@ -168,7 +144,7 @@ __global__ __launch_bounds__(TILE) void offsets_kernel(int32_t *__restrict__ cou
   for (unsigned tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const unsigned i = tile * (unsigned)TILE + threadIdx.x;
     const u64 own = i < n_bricks ? (u64)(unsigned)counts[i] : 0ull;
-    const u64 incl = block_scan(own, sums);
+    const u64 incl = side_block_scan(own, sums);
     if (i < n_bricks) counts[i] = (int32_t)(tile_sums[tile] + incl - own);
   }
 }
@@ -234,16 +210,13 @@ Layout layout(int64_t n_bricks, int64_t n_index) {
 }
 
 int counts_ok(const char *fn, int64_t n_tbars, int64_t n_bricks, int64_t n_index) {
-  const int64_t lim = 2147483647;
-  if (n_tbars < 0 || n_tbars > lim / 3)
+  if (n_tbars < 0 || n_tbars > SIDE_INT32_MAX / 3)
     return fplp_fail("%s: n_tbars %lld must lie in [0, %lld]", fn, (long long)n_tbars,
-                     (long long)(lim / 3));
-  if (n_bricks < 1 || n_bricks + 1 > lim)
+                     (long long)(SIDE_INT32_MAX / 3));
+  if (n_bricks < 1 || n_bricks + 1 > SIDE_INT32_MAX)
     return fplp_fail("%s: %lld bricks: int32 offsets index 1 to 2^31 - 2 bricks", fn,
                      (long long)n_bricks);
-  if (n_index < 0 || n_index > lim)
-    return fplp_fail("%s: n_index %lld must lie in [0, 2^31 - 1]", fn, (long long)n_index);
-  return 0;
+  return in_int32_range(fn, "n_index", n_index, 0);
 }
 
 unsigned blocks_for(int64_t waves, unsigned cap) {

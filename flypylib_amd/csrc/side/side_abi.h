@@ -2,7 +2,8 @@
 // error text behind <prefix>_last_error(), the guard of every entry point and the argument
 // checks more than one library makes.  Everything has internal linkage, so each library that
 // includes this header has an error buffer of its own.  Only launched() needs HIP: the rest
-// compiles with a plain host compiler, which is how tests/test_sidelib.py drives it.
+// compiles with a plain host compiler, which is how tests/test_sidelib.py drives it.  What the
+// libraries' kernels share is in side_device.h.
 //
 // A library keeps its own spelling as one-line aliases of SIDE_EXPORT, SIDE_CATCH and
 // side_fail, and defines its own <prefix>_last_error (returning side_err) and
@@ -47,11 +48,21 @@ inline int side_fail_exception(const char *fn) {
 
 inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+// what an int32 row, count or index can hold
+constexpr int64_t SIDE_INT32_MAX = 2147483647;
+
+// 0, or a message when `what` (a count: lo 1, a capacity: lo 0) lies outside [lo, 2^31 - 1]
+inline int in_int32_range(const char *fn, const char *what, int64_t v, int lo) {
+  if (v < lo || v > SIDE_INT32_MAX)
+    return side_fail("%s: %s %lld must lie in [%d, 2^31 - 1]", fn, what, (long long)v, lo);
+  return 0;
+}
+
 // *n = the voxels of a volume of positive dims, or a message when they exceed the 2^31 - 1 that
 // `what` ("the brick tables", ...) can index; `advice` says what to do instead
 inline int volume_voxels(const char *fn, const int64_t dims[3], const char *what, const char *advice,
                          int64_t *n) {
-  const int64_t lim = 2147483647;
+  const int64_t lim = SIDE_INT32_MAX;
   if (dims[0] > lim || dims[1] > lim || dims[2] > lim || dims[1] * dims[2] > lim ||
       dims[0] * (dims[1] * dims[2]) > lim)
     return side_fail("%s: a volume of (%lld,%lld,%lld) voxels exceeds the 2^31 - 1 voxels %s can "

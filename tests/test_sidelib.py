@@ -2,6 +2,7 @@
 each binding uses it, and csrc/side/side_abi.h driven by a host program of its own."""
 import inspect
 import os
+import re
 import shutil
 import subprocess
 
@@ -134,6 +135,22 @@ int main() {
   EXPECT(n == -1);
   EXPECT(!strcmp(side_err, "fn: a volume of (1,2147483648,1) voxels exceeds the 2^31 - 1 voxels "
                            "the brick tables can index; render it in parts"));
+
+  EXPECT(SIDE_INT32_MAX == 2147483647ll);
+  side_fail("untouched");
+  EXPECT(in_int32_range("fn", "n_gt", 1, 1) == 0);
+  EXPECT(in_int32_range("fn", "n_gt", 2147483647ll, 1) == 0);
+  EXPECT(in_int32_range("fn", "capacity", 0, 0) == 0);
+  EXPECT(in_int32_range("fn", "capacity", 2147483647ll, 0) == 0);
+  EXPECT(!strcmp(side_err, "untouched"));
+  EXPECT(in_int32_range("fn", "n_gt", 1ll << 31, 1) == 1);
+  EXPECT(!strcmp(side_err, "fn: n_gt 2147483648 must lie in [1, 2^31 - 1]"));
+  EXPECT(in_int32_range("fn", "n_gt", 0, 1) == 1);
+  EXPECT(!strcmp(side_err, "fn: n_gt 0 must lie in [1, 2^31 - 1]"));
+  EXPECT(in_int32_range("fn", "capacity", -1, 0) == 1);
+  EXPECT(!strcmp(side_err, "fn: capacity -1 must lie in [0, 2^31 - 1]"));
+  EXPECT(in_int32_range("fn", "capacity", 1ll << 31, 0) == 1);
+  EXPECT(!strcmp(side_err, "fn: capacity 2147483648 must lie in [0, 2^31 - 1]"));
   puts("side_abi ok");
   return 0;
 }
@@ -168,3 +185,9 @@ def test_side_abi_header_by_a_host_driver(tmp_path):
                               ('labels', 'the brick tables', 'render it in parts')):
         text = open(os.path.join(ROOT, 'flypylib_amd', 'csrc', sub, sub + '.hip')).read()
         assert 'volume_voxels(fn, dims, "%s", "%s", &' % (what, advice) in text
+    # the one block scan is csrc/side/side_device.h's, which belongs to no library either
+    for sub in ('mine', 'match', 'near', 'assign'):
+        text = open(os.path.join(ROOT, 'flypylib_amd', 'csrc', sub, sub + '.hip')).read()
+        assert 'side_scan_kernel' in text and 'void scan_kernel(' not in text, sub
+    device = open(os.path.join(ROOT, 'flypylib_amd', 'csrc', 'side', 'side_device.h')).read()
+    assert not re.search(r'\bfpl[a-z]?_', device, re.I)
