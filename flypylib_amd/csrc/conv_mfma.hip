@@ -2224,7 +2224,9 @@ int fpl_tm_conv3_split(fpl_ctx *ctx, const float *x, int n, int D, int H, int W_
     ts_maxabs<<<8, 256, 0, st>>>(Wd, (int64_t)27 * cin * cout, wmax);
   }
   for (int co0 = 0; co0 < Co;) {                 // 64, 48 or 32 output channels per launch
-    const int rem = Co - co0, MB = rem >= 64 ? 4 : rem / 16;
+    // (80 left go 48 + 32: 64 would leave 16, which no launch takes - the input gradient of
+    // unet_like_vol's 80 -> 32)
+    const int rem = Co - co0, MB = rem == 80 ? 3 : rem >= 64 ? 4 : rem / 16;
     FPL_REQUIRE(ctx, MB >= 2 && MB <= 4, "conv3 (split training): %d output channels left", rem);
     const int64_t wtotal = (int64_t)(Ci / 8) * u8::KP * 2 * MB * 512;
     FPL_TRY(tmp.alloc((size_t)wtotal * 2, &q));

@@ -488,6 +488,27 @@ __global__ void relu_bwd(const float *__restrict__ dy, const float *__restrict__
   if (i < n) dx[i] += y[i] > 0.f ? dy[i] : 0.f;
 }
 
+// Gradient through a convolution's fused ReLU, in place on the gradient of its output:
+// dy = y > 0 ? dy : 0 with y the post-activation value (relu_bwd's predicate).  Two reads
+// and one write of 16 B per thread and trip, grid-stride; the scalar form takes the
+// n % 4 elements behind the last whole float4.
+__global__ __launch_bounds__(256) void relu_mask_grad(const float4 *__restrict__ y,
+                                                      float4 *__restrict__ dy, int64_t n4) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 v = y[i];
+    float4 d = dy[i];
+    d.x = v.x > 0.f ? d.x : 0.f; d.y = v.y > 0.f ? d.y : 0.f;
+    d.z = v.z > 0.f ? d.z : 0.f; d.w = v.w > 0.f ? d.w : 0.f;
+    dy[i] = d;
+  }
+}
+__global__ void relu_mask_grad_tail(const float *__restrict__ y, float *__restrict__ dy,
+                                    int64_t i0, int64_t n) {
+  const int64_t i = i0 + threadIdx.x;
+  if (i < n) dy[i] = y[i] > 0.f ? dy[i] : 0.f;
+}
+
 __global__ void pool2_fwd(const float *__restrict__ x, float *__restrict__ y,
                           uint8_t *__restrict__ arg, int64_t n_out, int D, int H,
                           int W, int C, int od, int oh, int ow) {
@@ -891,8 +912,20 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
       FPL_REQUIRE(ctx, L.w_off[0] >= 0 && L.w_off[0] + kk <= n_weights &&
                            (!L.use_bias || (L.w_off[1] >= 0 && L.w_off[1] + L.cout <= n_weights)),
                   "layer %d: weight offsets exceed the arena", i);
-      FPL_REQUIRE(ctx, L.act == FPL_ACT_NONE || (L.act == FPL_ACT_SIGMOID && L.dst == out_tensor),
-                  "layer %d: only a sigmoid head may carry a conv activation", i);
+      FPL_REQUIRE(ctx, L.act == FPL_ACT_NONE || L.act == FPL_ACT_RELU || L.act == FPL_ACT_SIGMOID,
+                  "layer %d: unknown conv activation %d", i, L.act);
+      FPL_REQUIRE(ctx, L.act != FPL_ACT_SIGMOID || L.dst == out_tensor,
+                  "layer %d: only the head may carry a sigmoid activation", i);
+      FPL_REQUIRE(ctx, L.act != FPL_ACT_RELU || L.dst != out_tensor,
+                  "layer %d: the head needs a sigmoid activation (the losses are written "
+                  "for it), not a relu", i);
+      // the convolutions' fused BatchNorm-statistics epilogues and the BN passes that
+      // recompute a gradient from the conv's input are written for a linear conv output
+      if (L.act == FPL_ACT_RELU)
+        for (int j = 0; j < n_layers; ++j)
+          FPL_REQUIRE(ctx, !(layers[j].kind == FPL_L_BN && layers[j].src0 == L.dst),
+                      "layer %d: a conv with a relu activation feeding BatchNorm (layer %d) "
+                      "is not trainable", i, j);
     } else if (L.kind == FPL_L_BN) {
       FPL_REQUIRE(ctx, L.cin <= 256, "layer %d: > 256 channels", i);
       for (int q = 0; q < 4; ++q)
@@ -1062,6 +1095,10 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   std::vector<float *> bn_mean(nl, nullptr), bn_invstd(nl, nullptr);
   std::vector<double *> conv_stats(nt, nullptr);     // per tensor: statistics partials
   std::vector<int> conv_stats_rows(nt, 0);
+  // FPL_TRAIN_CONVRELU_SEPARATE (A/B): a conv's ReLU as passes of their own - the conv
+  // kernel without activation into pre[dst], relu_fwd, and relu_bwd in the backward pass
+  const bool relu_separate = getenv("FPL_TRAIN_CONVRELU_SEPARATE") != nullptr;
+  std::vector<float *> pre(nt, nullptr);
   auto alloc_f = [&](int64_t n, float **p) -> int {
     void *q;
     int rc = tmp.alloc((size_t)n * sizeof(float), &q);
@@ -1179,6 +1216,12 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
       case FPL_L_CONV: {
         const int64_t n_vox = (int64_t)batch * o.vox();
         const float *bias = L.use_bias ? t->w + L.w_off[1] : t->zeros;
+        // the activation (ReLU, or the head's sigmoid) is applied in the epilogue of
+        // whichever kernel runs below
+        const bool sep = L.act == FPL_ACT_RELU && relu_separate;
+        const int act = sep ? FPL_ACT_NONE : L.act;
+        if (sep) FPL_TRY(alloc_f(n, &pre[L.dst]));
+        float *yout = sep ? pre[L.dst] : val[L.dst];
         if (use_mfma && fpl_tm_supported(L.k, L.cin, L.cout)) {
           // a BatchNorm next in line gets its batch statistics from this kernel's epilogue
           double *st_part = nullptr;
@@ -1197,19 +1240,23 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
           const bool viewed = bn_view[L.src0] >= 0;
           const float *xin = viewed ? view_of(L.src0, &bv) : val[L.src0];
           FPL_TRY(fpl_tm_conv_fwd(ctx, xin, batch, a.d, a.h, a.w, a.c, L.k, L.cout,
-                                  t->w + L.w_off[0], bias, L.act, val[L.dst], st_part,
+                                  t->w + L.w_off[0], bias, act, yout, st_part,
                                   viewed ? &bv : nullptr));
-          break;
-        }
-        TimedLaunch tl(ctx, "train_conv_fwd");
-        if (L.cout % 16 == 0) {
-          dim3 g((unsigned)ceil_div64(n_vox, 256), L.cout / 16);
-          conv3d_direct_f32<16><<<g, 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
-              val[L.dst], n_vox, a.d, a.h, a.w, a.c, o.d, o.h, o.w, o.c, L.k, L.act);
         } else {
-          dim3 g((unsigned)ceil_div64(n_vox, 256), L.cout);
-          conv3d_direct_f32<1><<<g, 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
-              val[L.dst], n_vox, a.d, a.h, a.w, a.c, o.d, o.h, o.w, o.c, L.k, L.act);
+          TimedLaunch tl(ctx, "train_conv_fwd");
+          if (L.cout % 16 == 0) {
+            dim3 g((unsigned)ceil_div64(n_vox, 256), L.cout / 16);
+            conv3d_direct_f32<16><<<g, 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
+                yout, n_vox, a.d, a.h, a.w, a.c, o.d, o.h, o.w, o.c, L.k, act);
+          } else {
+            dim3 g((unsigned)ceil_div64(n_vox, 256), L.cout);
+            conv3d_direct_f32<1><<<g, 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
+                yout, n_vox, a.d, a.h, a.w, a.c, o.d, o.h, o.w, o.c, L.k, act);
+          }
+        }
+        if (sep) {
+          TimedLaunch tl(ctx, "train_elementwise");
+          relu_fwd<<<g1(n), 256, 0, st>>>(pre[L.dst], val[L.dst], n);
         }
         break;
       }
@@ -1386,6 +1433,32 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
       case FPL_L_CONV: {
         const int64_t n_vox = (int64_t)batch * o.vox();
         const int taps = L.k * L.k * L.k;
+        if (L.act == FPL_ACT_RELU && relu_separate) {
+          float *dpre;
+          FPL_TRY(alloc_f(n, &dpre));
+          FPL_HIP(ctx, hipMemsetAsync(dpre, 0, (size_t)n * 4, st));
+          TimedLaunch tl(ctx, "train_elementwise");
+          relu_bwd<<<g1(n), 256, 0, st>>>(dy, val[L.dst], dpre, n);
+          dy = dpre;
+        } else if (L.act == FPL_ACT_RELU) {
+          // The gradient of the pre-activation, in place: dy *= (y > 0).  Safe because
+          //  - the layers run in reverse, so every consumer of L.dst (several for a skip
+          //    connection: unet_like_vol's c1 feeds a pool and a crop) has already added its
+          //    share to grad[L.dst], and this conv is the tensor's only producer: nobody
+          //    reads or writes that gradient after this layer;
+          //  - it runs before anything copies dy: the split-half kernels cache planar
+          //    copies by device pointer for the whole step (conv_mfma.hip, split_copy), and
+          //    the only copies of grad[L.dst] are made by this layer's own weight- and
+          //    input-gradient calls below.  A copy of the unmasked gradient would be stale.
+          // The bias gradient and every kernel below then read the masked dy as it is.
+          const int64_t n4 = n / 4;
+          TimedLaunch tl(ctx, "train_elementwise");
+          if (n4 > 0) {
+            const unsigned gr = (unsigned)std::min<int64_t>(ceil_div64(n4, 256), (int64_t)ctx->n_cu * 8);
+            relu_mask_grad<<<gr, 256, 0, st>>>((const float4 *)val[L.dst], (float4 *)dy, n4);
+          }
+          if (n % 4) relu_mask_grad_tail<<<1, 64, 0, st>>>(val[L.dst], dy, 4 * n4, n);
+        }
         if (use_mfma_bwd && fpl_tm_bwd_supported(L.k, L.cin, L.cout)) {
           FplBnView bv;
           const bool viewed = bn_view[L.src0] >= 0;
@@ -1643,15 +1716,16 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   if (const char *dump = getenv("FPL_TRAIN_DUMP")) {
     // debug: raw fp32 dump of every activation / activation-gradient tensor
     FPL_HIP(ctx, hipStreamSynchronize(st));
+    // (pre_*: the pre-activation of a ReLU conv, kept only by FPL_TRAIN_CONVRELU_SEPARATE)
     for (int ti = 1; ti < nt; ++ti) {
-      for (int which = 0; which < 2; ++which) {
-        const float *src = which ? grad[ti] : val[ti];
+      for (int which = 0; which < 3; ++which) {
+        const float *src = which == 2 ? pre[ti] : which ? grad[ti] : val[ti];
         if (!src) continue;
         const int64_t n = (int64_t)batch * shp[ti].elems();
         std::vector<float> h((size_t)n);
         FPL_HIP(ctx, hipMemcpy(h.data(), src, (size_t)n * 4, hipMemcpyDeviceToHost));
         char path[512];
-        snprintf(path, sizeof(path), "%s/%s_%03d_c%d.f32", dump, which ? "grad" : "val", ti, shp[ti].c);
+        snprintf(path, sizeof(path), "%s/%s_%03d_c%d.f32", dump, which == 2 ? "pre" : which ? "grad" : "val", ti, shp[ti].c);
         if (FILE *f = fopen(path, "wb")) { fwrite(h.data(), 4, (size_t)n, f); fclose(f); }
       }
     }

@@ -10,7 +10,10 @@ executes its lowered op list.  `vgg_like` and `unet_like2` are the two
 architectures of the BASELINE configs; the others use the same layer kinds.
 
 Losses/metrics are referred to by name; their arithmetic lives in the training
-engine (binary_crossentropy) or is a SURVEY section 8f follow-on (masked/focal).
+engine (`csrc/train.hip`: binary_crossentropy, the masked / weighted / focal losses and
+the masked metrics).  All ten factories train; `unet_like_vol`'s ReLU-activated
+convolutions are one conv layer each there (activation in the kernel epilogue, the
+gradient masked in place in the backward pass).
 """
 import math
 

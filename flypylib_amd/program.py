@@ -417,13 +417,11 @@ def lower_training(graph):
                  cout=n.channels, use_bias=0, act=ACT_NONE, rate=0.0, p=(0,) * 6,
                  w_off=[0, 0, 0, 0])
         if n.kind == 'conv':
-            a = n.attrs['activation']
-            if a == 'relu':
-                raise NotImplementedError(
-                    'conv with a fused relu activation (unet_like_vol) is not '
-                    'trainable yet')
+            # a fused relu (unet_like_vol) stays one layer: the engine applies it in the conv
+            # epilogue and masks the arriving gradient in the backward pass
             d.update(k=n.attrs['k'], use_bias=int(n.attrs['use_bias']),
-                     act={None: ACT_NONE, 'sigmoid': ACT_SIGMOID}[a])
+                     act={None: ACT_NONE, 'relu': ACT_RELU,
+                          'sigmoid': ACT_SIGMOID}[n.attrs['activation']])
             d['w_off'][0] = offsets[n.weight_slots[0]]
             if n.attrs['use_bias']:
                 d['w_off'][1] = offsets[n.weight_slots[1]]

@@ -254,7 +254,10 @@ typedef struct fpl_layer {
   int32_t dst;
   int32_t k, cin, cout;/* conv                                                 */
   int32_t use_bias;    /* conv                                                 */
-  int32_t act;         /* conv activation (fpl_act); sigmoid only on the head  */
+  int32_t act;         /* conv activation (fpl_act): relu on any conv but the
+                        * head (applied in the conv epilogue, its gradient masked
+                        * in place in the backward pass; not in front of a BN),
+                        * sigmoid on the head and only there                    */
   float rate;          /* dropout                                              */
   int32_t p[6];        /* pool/up factors or crop pairs                        */
   int64_t w_off[4];    /* offsets (floats) into the weight arena: conv kernel,

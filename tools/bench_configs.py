@@ -49,6 +49,13 @@
             (near.pairs_device; the whole call, and the key kernel, torch.sort, count + scan
             and fill alone by HIP events), and the whole call per method (dense at 3 000 only);
             median, min and max over --dedupe-reps runs; written to profiles/dedupe.json
+  train_vol unet_like_vol training step at the factory's 62^3 patches (50^3 outputs), loss
+            masked_weighted_binary_crossentropy, at the largest batch of 32 / 16 / 8 that fits:
+            the default (ReLU in the conv epilogues, the gradient masked in place) against
+            FPL_TRAIN_CONVRELU_SEPARATE=1 (conv, relu_fwd, relu_bwd as passes of their own), the
+            two legs alternating in one process on one trainer; median, min and max of the
+            rounds' ms per step and the per-kernel table of each leg; written to
+            profiles/train_vol.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -62,6 +69,73 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def train_vol(ctx, rounds=7, steps=8):
+    """ms per unet_like_vol training step (step + Adam, constant host batch, H2D inside), the
+    fused default against FPL_TRAIN_CONVRELU_SEPARATE=1.  The library reads the switch at every
+    step, so both legs run on one trainer, alternating round by round (drift hits both alike)."""
+    from flypylib_amd import _capi, fplmodels, synth
+    g = fplmodels.unet_like_vol()[0]
+    synth.synthetic_weights(g, 3)
+    loss = 'masked_weighted_binary_crossentropy'
+    rng = np.random.default_rng(0)
+    out = None
+    for batch in (32, 16, 8):
+        data = rng.standard_normal((batch, 62, 62, 62, 1)).astype(np.float32)
+        labels = rng.integers(0, 3, (batch, 50, 50, 50, 1)).astype(np.uint8)
+        tr = _capi.Trainer(ctx, g, loss=loss)
+        legs = (('fused', None), ('separate', '1'))
+
+        def run(env, n, seed0):
+            if env is None:
+                os.environ.pop('FPL_TRAIN_CONVRELU_SEPARATE', None)
+            else:
+                os.environ['FPL_TRAIN_CONVRELU_SEPARATE'] = env
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for s in range(n):
+                tr.step(data, labels, seed0 + s); tr.apply(1.0)
+            ctx.synchronize()
+            return (time.perf_counter() - t0) / n * 1e3
+        try:
+            for _, env in legs:                       # warm-up: both legs' buffers exist
+                run(env, 2, 0)
+        except _capi.FplHipError as e:
+            print('train_vol: batch %d does not fit (%s)' % (batch, e), flush=True)
+            tr.close()
+            continue
+        ms = {name: [] for name, _ in legs}
+        for r in range(rounds):
+            for name, env in legs:
+                ms[name].append(run(env, steps, 10 + r * steps))
+        kern = {}
+        for name, env in legs:                        # per-kernel events: runs of their own
+            ctx.timing(True); ctx.timing_reset()
+            run(env, 3, 1000)
+            kern[name] = {k: round(v['ms'] / 3, 3) for k, v in ctx.timing_get().items()}
+            ctx.timing(False)
+        os.environ.pop('FPL_TRAIN_CONVRELU_SEPARATE', None)
+        tr.close()
+        out = {'batch': batch, 'patch': 62, 'loss': loss, 'rounds': rounds, 'steps_per_round': steps,
+               'note': 'ms per step (forward, loss, backward, Adam; host batch, H2D inside), legs '
+                       'alternating round by round on one trainer'}
+        for name, _ in legs:
+            v = ms[name]
+            out[name] = {'median_ms': round(float(np.median(v)), 3), 'min_ms': round(min(v), 3),
+                         'max_ms': round(max(v), 3), 'rounds_ms': [round(x, 3) for x in v],
+                         'kernels_ms': kern[name]}
+        f, sp = out['fused'], out['separate']
+        out['separate_over_fused'] = round(sp['median_ms'] / f['median_ms'], 4)
+        # the expectation: the default is not slower than the separate passes beyond the
+        # run-to-run spread of the two legs
+        spread = max(f['max_ms'] - f['min_ms'], sp['max_ms'] - sp['min_ms'])
+        out['spread_ms'] = round(spread, 3)
+        out['fused_not_slower_beyond_spread'] = bool(f['median_ms'] <= sp['median_ms'] + spread)
+        break
+    if out is None:
+        raise RuntimeError('train_vol: no batch of 32 / 16 / 8 fits')
+    return out
 
 
 def train_gen(ctx, torch, steps=30, vol=200):
@@ -839,6 +913,12 @@ def main():
         res['labels'] = labels_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'labels.json')
+
+    if 'train_vol' in what:
+        res['train_vol'] = train_vol(ctx)
+        print(json.dumps(res['train_vol']), flush=True)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'train_vol.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
