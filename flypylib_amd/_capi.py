@@ -12,9 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libfplhip.so')
 
 MEM_HOST, MEM_DEVICE = 0, 1
+MEM_DEVICE_BOX = 2           # fpl_v2o_set_seg: `seg` is a fpl_seg_box
 U8, F32, F64 = 0, 1, 2
 PREC_AUTO, PREC_F32, PREC_BF16, PREC_F16, PREC_F16S = -1, 0, 1, 2, 3
-ABI_VERSION = 8
+ABI_VERSION = 9
 COMM_ID_BYTES = 128
 
 
@@ -36,6 +37,10 @@ class fpl_layer(C.Structure):
                 ('cout', C.c_int32), ('use_bias', C.c_int32), ('act', C.c_int32),
                 ('rate', C.c_float), ('p', C.c_int32 * 6),
                 ('w_off', C.c_int64 * 4)]
+
+
+class fpl_seg_box(C.Structure):
+    _fields_ = [('vol', C.c_void_p), ('extent', C.c_int64 * 3), ('origin', C.c_int64 * 3)]
 
 
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -243,6 +248,25 @@ def host_empty(shape, dtype=np.float32):
     return _host_pool.empty(shape, dtype)
 
 
+def resident_labels(vol, who='seg'):
+    """(bytes per label, extents) of a device-resident (Z,Y,X) label volume: a contiguous torch
+    CUDA tensor or a `DeviceBuffer` of 4- or 8-byte integers; anything else raises ValueError
+    naming the argument `who` stands for"""
+    if isinstance(vol, DeviceBuffer):
+        dt = vol.dtype
+        ok, nbytes = dt.kind in 'iu', dt.itemsize
+    elif getattr(vol, 'is_cuda', False) and hasattr(vol, 'is_contiguous'):
+        ok = vol.is_contiguous() and not vol.dtype.is_floating_point and not vol.dtype.is_complex
+        nbytes = vol.element_size()
+    else:
+        raise ValueError('%s: the label volume must be device resident (a torch CUDA tensor or a '
+                         'DeviceBuffer), got %s' % (who, type(vol).__name__))
+    if not ok or nbytes not in (4, 8) or len(vol.shape) != 3:
+        raise ValueError('%s: a resident label volume is a contiguous (Z,Y,X) array of 4- or 8-byte '
+                         'integers, got %s %s' % (who, vol.dtype, tuple(vol.shape)))
+    return nbytes, tuple(int(s) for s in vol.shape)
+
+
 class Context:
     """one GPU (fpl_ctx).  Create after fork(); use from one thread at a time."""
 
@@ -418,6 +442,23 @@ class Context:
         self.check(self.lib.fpl_v2o_set_seg(self.h, _ptr(seg), nbytes, _mem_of(seg),
                                             _arr(dims, C.c_int64),
                                             -1 if sz_thd is None else int(sz_thd)))
+
+    def v2o_set_seg_box(self, vol, origin, dims, sz_thd=None):
+        """v2o_set_seg from a label volume RESIDENT on this GPU (see `resident_labels`): the
+        box `origin` .. `origin + dims` (z, y, x) of it, zeros where it leaves the volume
+        (fpl_v2o_set_seg with FPL_MEM_DEVICE_BOX)"""
+        nbytes, extent = resident_labels(vol, 'v2o_set_seg_box')
+        box = fpl_seg_box(_ptr(vol).value, _arr(extent, C.c_int64), _arr(origin, C.c_int64))
+        self.check(self.lib.fpl_v2o_set_seg(self.h, C.cast(C.byref(box), _vp), nbytes, MEM_DEVICE_BOX,
+                                            _arr(dims, C.c_int64),
+                                            -1 if sz_thd is None else int(sz_thd)))
+
+    def gather_labels(self, vol, zyx, out=None):
+        """uint64 labels of the resident label volume `vol` at the (n, 3) int64 (z, y, x)
+        points `zyx` (host array or device tensor); a point outside the volume raises
+        (libfplseg.so, `_segcapi.gather_labels`)"""
+        from . import _segcapi
+        return _segcapi.gather_labels(vol, zyx, out)
 
     def v2o_select(self, ranks):
         ranks = np.ascontiguousarray(ranks, np.int64)

@@ -33,7 +33,12 @@ The three tables above are pinned by their tests; its binding loads lazily as we
 SOLVE_LIBRARIES is a fifth table of that shape, beside EVAL_LIBRARIES: libfplassign.so solves
 the matching on the pair table libfplmatch.so leaves on the device (solver='device').  The four
 tables above and ALL_TABLES are pinned by their tests, so its row is a table of its own;
-EVERY_LIBRARY is what build() walks.
+EVERY_LIBRARY is their union.
+
+LABEL_LIBRARIES is a sixth table of that shape, for reads of a resident label volume: libfplseg.so
+gathers the labels of points and pads a box of the volume.  EVERY_LIBRARY is pinned as well, so
+BUILT_LIBRARIES is what build() walks.  Its source shares csrc/seg_box.h with libfplhip.so, so
+the headers of csrc/ are part of its stamp.
 """
 import argparse
 import hashlib
@@ -68,6 +73,10 @@ SOLVE_LIBRARIES = (
 )
 ALL_TABLES = SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES + POST_LIBRARIES
 EVERY_LIBRARY = ALL_TABLES + SOLVE_LIBRARIES
+LABEL_LIBRARIES = (
+    ('seg', 'seg', 'fpls', 'fplseg.h', 'libfplseg.so'),                # labels of a resident volume
+)
+BUILT_LIBRARIES = EVERY_LIBRARY + LABEL_LIBRARIES
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -185,22 +194,24 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in EVERY_LIBRARY:
+    for row in BUILT_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES or
-    SOLVE_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the
+    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
+    SOLVE_LIBRARIES or LABEL_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the
     row's prefix only"""
-    _, sub, prefix, header, lib = next(r for r in EVERY_LIBRARY if r[0] == key)
+    row = next(r for r in BUILT_LIBRARIES if r[0] == key)
+    _, sub, prefix, header, lib = row
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]
     return _build_library(os.path.join(LIB_DIR, lib), prefix + '_*', srcs, src_dir,
                           _digest(_local_headers(src_dir)
                                   + _local_headers(os.path.join(HERE, 'side'))
+                                  + (_local_headers(HERE) if row in LABEL_LIBRARIES else [])
                                   + [os.path.join(inc, header)]),
                           force, jobs, verbose)
 

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "seg_box.h"
 
 // The smoothing must round every product and every sum on its own, as scipy's C does on
 // x86-64.  hipcc's default for device code fuses a * b + c into v_fma_f64 across
@@ -1787,28 +1788,9 @@ int fpl_v2o_nms_seg(fpl_ctx *ctx, double thresh, int32_t seg_dilate, int32_t seg
   return v2o_nms(ctx, thresh, out_zyxv, cap, n_out, n_rounds, true, seg_dilate, seg_force);
 } FPL_CATCH(ctx)
 
-int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_mem,
-                    const int64_t dims[3], int64_t sz_thd) try {
-  if (!ctx || !seg || !dims) return fpl_fail(ctx, "fpl_v2o_set_seg: NULL argument");
+// room for the padded u64 segmentation of the current smoothed volume
+static int v2o_seg_reserve(fpl_ctx *ctx, int64_t n_pad) {
   V2oState &S = ctx->v2o;
-  FPL_REQUIRE(ctx, S.valid, "fpl_v2o_set_seg: call fpl_v2o_smooth first");
-  FPL_REQUIRE(ctx, seg_bytes == 4 || seg_bytes == 8, "fpl_v2o_set_seg: labels must be 4 or 8 bytes");
-  const int r = S.r;
-  for (int a = 0; a < 3; ++a)
-    FPL_REQUIRE(ctx, dims[a] + 2 * r == S.pdims[a],
-                "fpl_v2o_set_seg: segmentation dims differ from the prediction's");
-  FPL_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  DevTemp tmp(ctx);
-  const int64_t n = dims[0] * dims[1] * dims[2];
-  const int64_t n_pad = S.pdims[0] * S.pdims[1] * S.pdims[2];
-  const void *src = seg;
-  if (seg_mem == FPL_MEM_HOST) {
-    void *p;
-    FPL_TRY(tmp.alloc((size_t)n * seg_bytes, &p));
-    FPL_HIP(ctx, hipMemcpyAsync(p, seg, (size_t)n * seg_bytes, hipMemcpyHostToDevice, st));
-    src = p;
-  }
   const size_t need = (size_t)n_pad * sizeof(unsigned long long);
   if (S.seg_cap_bytes < need) {
     if (S.seg) fpl_dev_release(ctx, S.seg);
@@ -1817,16 +1799,17 @@ int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_me
     FPL_TRY(fpl_dev_alloc(ctx, need, &p));
     S.seg = (unsigned long long *)p; S.seg_cap_bytes = need;
   }
+  return 0;
+}
+
+// what follows the fill of S.seg, whichever entry point made it (`who`, for the messages):
+// with sz_thd >= 0 the voxel count per label and the zeroing of small segments
+static int v2o_seg_finish(fpl_ctx *ctx, int64_t sz_thd, const char *who) {
+  V2oState &S = ctx->v2o;
+  hipStream_t st = ctx->stream;
+  DevTemp tmp(ctx);
+  const int64_t n_pad = S.pdims[0] * S.pdims[1] * S.pdims[2];
   const unsigned grid = (unsigned)ceil_div64(n_pad, 256);
-  {
-    TimedLaunch tl(ctx, "v2o_seg_pad");
-    if (seg_bytes == 8)
-      seg_pad<unsigned long long><<<grid, 256, 0, st>>>((const unsigned long long *)src, dims[0],
-          dims[1], dims[2], r, S.seg, S.pdims[1], S.pdims[2], n_pad);
-    else
-      seg_pad<uint32_t><<<grid, 256, 0, st>>>((const uint32_t *)src, dims[0], dims[1], dims[2],
-          r, S.seg, S.pdims[1], S.pdims[2], n_pad);
-  }
   FPL_HIP(ctx, hipGetLastError());
   if (sz_thd >= 0) {
     S.cellmax_valid = false;      // the volume is edited below: the fused cell keys are stale
@@ -1850,7 +1833,7 @@ int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_me
     unsigned int ovf = 0;
     FPL_HIP(ctx, hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, st));
     FPL_HIP(ctx, hipStreamSynchronize(st));
-    FPL_REQUIRE(ctx, ovf == 0, "fpl_v2o_set_seg: more than %llu distinct labels",
+    FPL_REQUIRE(ctx, ovf == 0, "%s: more than %llu distinct labels", who,
                 (unsigned long long)cap);
     {
       TimedLaunch tl(ctx, "v2o_seg_zero_small");
@@ -1868,6 +1851,71 @@ int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_me
   FPL_HIP(ctx, hipStreamSynchronize(st));
   S.seg_valid = true;
   return 0;
+}
+
+// fpl_v2o_set_seg with FPL_MEM_DEVICE_BOX: the padded segmentation filled by one kernel from the
+// box of a resident label volume that `box` describes - no cube, no temporary
+static int v2o_set_seg_box(fpl_ctx *ctx, const fpl_seg_box *box, int32_t seg_bytes,
+                           const int64_t dims[3], int64_t sz_thd) {
+  V2oState &S = ctx->v2o;
+  FPL_REQUIRE(ctx, box->vol, "fpl_v2o_set_seg: the box descriptor's volume is NULL");
+  for (int a = 0; a < 3; ++a)
+    FPL_REQUIRE(ctx, dims[a] > 0 && dims[a] < ((int64_t)1 << 21) && box->extent[a] > 0 &&
+                         box->extent[a] < ((int64_t)1 << 21) &&
+                         box->origin[a] > -((int64_t)1 << 21) && box->origin[a] < ((int64_t)1 << 21),
+                "fpl_v2o_set_seg: box axis %d out of the 2^21 coordinate range", a);
+  FPL_HIP(ctx, hipSetDevice(ctx->device));
+  hipPointerAttribute_t attr;
+  const hipError_t pe = hipPointerGetAttributes(&attr, box->vol);
+  if (pe != hipSuccess) (void)hipGetLastError();          // plain host memory on older runtimes
+  FPL_REQUIRE(ctx, pe == hipSuccess && attr.type == hipMemoryTypeDevice,
+              "fpl_v2o_set_seg: the label volume of a box must be device memory");
+  const int64_t n_pad = S.pdims[0] * S.pdims[1] * S.pdims[2];
+  FPL_TRY(v2o_seg_reserve(ctx, n_pad));
+  {
+    TimedLaunch tl(ctx, "v2o_seg_pad_box");
+    launch_seg_pad_box(box->vol, seg_bytes, box->extent, box->origin, S.r, S.seg, S.pdims, ctx->n_cu,
+                       ctx->stream);
+  }
+  return v2o_seg_finish(ctx, sz_thd, "fpl_v2o_set_seg");
+}
+
+int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_mem,
+                    const int64_t dims[3], int64_t sz_thd) try {
+  if (!ctx || !seg || !dims) return fpl_fail(ctx, "fpl_v2o_set_seg: NULL argument");
+  V2oState &S = ctx->v2o;
+  FPL_REQUIRE(ctx, S.valid, "fpl_v2o_set_seg: call fpl_v2o_smooth first");
+  FPL_REQUIRE(ctx, seg_bytes == 4 || seg_bytes == 8, "fpl_v2o_set_seg: labels must be 4 or 8 bytes");
+  const int r = S.r;
+  for (int a = 0; a < 3; ++a)
+    FPL_REQUIRE(ctx, dims[a] + 2 * r == S.pdims[a],
+                "fpl_v2o_set_seg: segmentation dims differ from the prediction's");
+  if (seg_mem == FPL_MEM_DEVICE_BOX)
+    return v2o_set_seg_box(ctx, (const fpl_seg_box *)seg, seg_bytes, dims, sz_thd);
+  FPL_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevTemp tmp(ctx);
+  const int64_t n = dims[0] * dims[1] * dims[2];
+  const int64_t n_pad = S.pdims[0] * S.pdims[1] * S.pdims[2];
+  const void *src = seg;
+  if (seg_mem == FPL_MEM_HOST) {
+    void *p;
+    FPL_TRY(tmp.alloc((size_t)n * seg_bytes, &p));
+    FPL_HIP(ctx, hipMemcpyAsync(p, seg, (size_t)n * seg_bytes, hipMemcpyHostToDevice, st));
+    src = p;
+  }
+  FPL_TRY(v2o_seg_reserve(ctx, n_pad));
+  const unsigned grid = (unsigned)ceil_div64(n_pad, 256);
+  {
+    TimedLaunch tl(ctx, "v2o_seg_pad");
+    if (seg_bytes == 8)
+      seg_pad<unsigned long long><<<grid, 256, 0, st>>>((const unsigned long long *)src, dims[0],
+          dims[1], dims[2], r, S.seg, S.pdims[1], S.pdims[2], n_pad);
+    else
+      seg_pad<uint32_t><<<grid, 256, 0, st>>>((const uint32_t *)src, dims[0], dims[1], dims[2],
+          r, S.seg, S.pdims[1], S.pdims[2], n_pad);
+  }
+  return v2o_seg_finish(ctx, sz_thd, "fpl_v2o_set_seg");   // `tmp` (the uploaded cube) outlives it
 } FPL_CATCH(ctx)
 
 int fpl_v2o_select(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, float *rank_values) try {

@@ -54,7 +54,7 @@ def percentile_lerp(lo, hi, gamma):
 def voxel2obj(pred, obj_min_dist, smoothing_sigma,
               volume_offset=(0, 0, 0), buffer_sz=0, thd=0,
               seg=None, seg_dilate=None, seg_sz_thd=None, seg_force=None,
-              device=None, return_info=False, _ctx=None):
+              device=None, return_info=False, seg_origin=None, _ctx=None):
     """convert voxel-wise predictions to object (point) predictions.
 
     pred: (Z,Y,X) float32 numpy array, or a float32 device tensor of that shape; a float64
@@ -74,8 +74,22 @@ def voxel2obj(pred, obj_min_dist, smoothing_sigma,
     within the (2r+1)^3 cube, grown by `seg_dilate` binary-dilation iterations - plus
     the ball of radius `seg_force`; `seg_sz_thd` first zeroes the smoothed prediction
     inside segments of fewer voxels (obj_min_dist <= 127 in this mode).
+
+    seg_origin=(z, y, x): `seg` is instead a label volume of ANY extents resident on the GPU - a
+    contiguous torch CUDA tensor or a `_capi.DeviceBuffer` of 4- or 8-byte integers - and pred's
+    box starts at `seg_origin` in it; labels where the box leaves the volume are 0.  The padded
+    segmentation is filled from the volume by one kernel (`fpl_v2o_set_seg` with a box descriptor), no cube is cut;
+    the result is that of passing the cut cube as `seg`.  A host `seg` then raises ValueError.
     """
     buffer_sz = fplutils.to3d(buffer_sz)
+    if seg_origin is not None:
+        from . import _capi
+        if seg is None:
+            raise ValueError('voxel2obj: seg_origin needs seg, a device-resident label volume')
+        _capi.resident_labels(seg, 'voxel2obj: seg (with seg_origin)')
+        seg_origin = tuple(int(v) for v in seg_origin)
+        if len(seg_origin) != 3:
+            raise ValueError('voxel2obj: seg_origin must be (z, y, x), got %r' % (seg_origin,))
     if isinstance(pred, str):
         pred = _load_main(pred)
     r = int(obj_min_dist)
@@ -112,10 +126,7 @@ def voxel2obj(pred, obj_min_dist, smoothing_sigma,
             ctx.v2o_set_integer(True)
         ctx.v2o_smooth_f64(pred, pred_sz, r, weights)
         if seg is not None:
-            if isinstance(seg, str):
-                seg = _load_main(seg)
-            assert tuple(int(v) for v in seg.shape) == pred_sz, 'seg must have pred\'s shape'
-            ctx.v2o_set_seg(seg, pred_sz, seg_sz_thd)
+            _set_seg(ctx, seg, seg_origin, pred_sz, seg_sz_thd)
         lo_v, hi_v = ctx.v2o_select_f64([lo_rank, hi_rank])
         thresh = np.maximum(percentile_lerp(lo_v, hi_v, gamma), thd)
         ctx.v2o_rank_f64(float(thresh))
@@ -139,11 +150,8 @@ def voxel2obj(pred, obj_min_dist, smoothing_sigma,
         thresh = np.maximum(percentile_lerp(lo_v, hi_v, gamma), thd)
         pts, rounds = ctx.v2o_nms(float(thresh))
     else:
-        if isinstance(seg, str):
-            seg = _load_main(seg)
-        assert tuple(int(v) for v in seg.shape) == pred_sz, 'seg must have pred\'s shape'
         ctx.v2o_smooth(pred, pred_sz, r, weights, [])
-        ctx.v2o_set_seg(seg, pred_sz, seg_sz_thd)           # pads; zeroes small segments
+        _set_seg(ctx, seg, seg_origin, pred_sz, seg_sz_thd)  # pads; zeroes small segments
         lo_v, hi_v = ctx.v2o_select([lo_rank, hi_rank])
         thresh = np.maximum(percentile_lerp(lo_v, hi_v, gamma), thd)
         pts, rounds = ctx.v2o_nms_seg(float(thresh), seg_dilate, seg_force)
@@ -175,6 +183,18 @@ def voxel2obj(pred, obj_min_dist, smoothing_sigma,
         return obj_out, dict(thresh=thresh, rounds=rounds,
                              ranks=(lo_rank, hi_rank), gamma=gamma)
     return obj_out
+
+
+def _set_seg(ctx, seg, seg_origin, pred_sz, seg_sz_thd):
+    """the padded segmentation of the smoothed volume: from labels of pred's shape, or - with
+    `seg_origin` - from pred's box of a resident label volume"""
+    if seg_origin is not None:
+        ctx.v2o_set_seg_box(seg, seg_origin, pred_sz, seg_sz_thd)
+        return
+    if isinstance(seg, str):
+        seg = _load_main(seg)
+    assert tuple(int(v) for v in seg.shape) == pred_sz, 'seg must have pred\'s shape'
+    ctx.v2o_set_seg(seg, pred_sz, seg_sz_thd)
 
 
 def _load_main(src):
@@ -601,8 +621,11 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
     device=<int> or True (the runtime's default device): the prediction is inferred into a
     resident float32 tensor (FplNetwork.infer(device=...)), voxel2obj reads it where it lies
     and obj_pr_curve(device=...) scores the points on the sparse pair table of
-    libfplmatch.so; the segmentation lookup stays on the host.  The results equal the host
-    call's.  Without torch, a GPU or the library the call raises.
+    libfplmatch.so.  A segmentation (`ss[2]`) may be a label volume resident on that GPU (a torch
+    CUDA tensor or a `_capi.DeviceBuffer` of 4- or 8-byte integers); a host one is uploaded once
+    per substack, and the points' labels are gathered there (`fpls_gather_labels`, libfplseg.so) at the
+    coordinates the host truncates.  The results equal the host call's.  Without torch, a GPU or
+    the library the call raises.
 
     solver: as for obj_pr; 'device' needs `device` and keeps the matching on the GPU as well."""
     from . import fplsynapses
@@ -623,7 +646,22 @@ def evaluate_substacks(network, substacks, thds, obj_min_dist=27, smoothing_sigm
                             device=dev.index)
         gt = fplsynapses.load_from_json(ss[1], tuple(pred.shape), buffer_sz)
         lbls_pd = lbls_gt = None
-        if len(ss) >= 3 and ss[2] is not None:
+        if len(ss) >= 3 and ss[2] is not None and dev is not None:
+            # the labels stay on (or go once to) the GPU; the truncated coordinates are the host's
+            from . import fplpipeline
+            ctx = runtime.get_context(dev.index)
+            seg = ss[2] if fplpipeline._is_device_volume(ss[2]) else np.asarray(_load_main(ss[2]))
+            seg_src = fplpipeline._open_label_source(seg)
+            mine = not isinstance(seg_src, fplpipeline._DeviceLabelSource)
+            if mine:
+                seg_src = fplpipeline._DeviceLabelSource.upload(ctx, seg_src)
+            try:
+                lbls_pd, lbls_gt = (seg_src.labels_at(ctx, tt['locs'].astype(int)[:, ::-1])
+                                    for tt in (out, gt))
+            finally:
+                if mine:
+                    seg_src.free()
+        elif len(ss) >= 3 and ss[2] is not None:
             seg = np.asarray(_load_main(ss[2]))
 
             def labels_at(tt):

@@ -164,9 +164,98 @@ class _DeviceSource:
         return True
 
 
+class _DeviceLabelSource:
+    """a (Z,Y,X) label volume RESIDENT in the GPU's memory: a contiguous torch CUDA tensor or a
+    `_capi.DeviceBuffer` of 4- or 8-byte integers.  voxel2obj fills its padded segmentation
+    straight from it (`seg=<vol>, seg_origin=...`: `fpl_v2o_set_seg` with a box descriptor), the labels of points
+    come from `fpls_gather_labels`; the host never cuts a label cube.  `dtype` is the numpy type
+    `labels_at` answers in: the volume's own, or that of the host array it was uploaded from."""
+
+    def __init__(self, vol, host_dtype=None):
+        from . import _capi
+        self.itemsize, self.extent = _capi.resident_labels(vol, 'the segmentation')
+        self.vol = vol
+        if isinstance(vol, _capi.DeviceBuffer):
+            self.device = vol.ctx.device
+            dtype = vol.dtype
+        else:
+            self.device = vol.device.index or 0
+            dtype = np.dtype(str(vol.dtype).replace('torch.', ''))
+        self.dtype = np.dtype(host_dtype) if host_dtype is not None else dtype
+
+    @classmethod
+    def upload(cls, ctx, src):
+        """the host array source `src` copied to `ctx`'s GPU in z slabs; dtypes other than 4- or
+        8-byte integers are converted to uint64 slab by slab"""
+        dt = np.dtype(src.arr.dtype)
+        dev_dt = dt if dt.kind in 'iu' and dt.itemsize in (4, 8) else np.dtype(np.uint64)
+        buf = ctx.malloc(src.extent, dev_dt)
+        try:
+            plane = int(src.extent[1]) * int(src.extent[2]) * dev_dt.itemsize
+            step = max(1, (256 << 20) // max(plane, 1))            # 256 MiB slabs: a memmap is read as it goes
+            for z0 in range(0, src.extent[0], step):
+                part = np.ascontiguousarray(src.arr[z0:min(src.extent[0], z0 + step)], dev_dt)
+                ctx.memcpy(buf.ptr + z0 * plane, part, part.nbytes)
+            ctx.synchronize()
+        except BaseException:
+            buf.free()
+            raise
+        return cls(buf, host_dtype=dt)
+
+    def labels_at(self, ctx, zyx):
+        """labels at the (n, 3) integer (z, y, x) points, as `arr[z, y, x]` of the host array
+        would give them; a point outside the volume raises"""
+        assert ctx.device == self.device, \
+            'the labels live on GPU %d, the context on GPU %d' % (self.device, ctx.device)
+        got = ctx.gather_labels(self.vol, zyx)
+        if self.itemsize == 4:
+            got = got.astype(np.uint32)
+        return got.view(np.dtype('%s%d' % ('i' if self.dtype.kind == 'i' else 'u', self.itemsize))
+                        ).astype(self.dtype, copy=False)
+
+    def free(self):
+        if hasattr(self.vol, 'free'):
+            self.vol.free()
+
+
 def _is_device_volume(v):
     from . import _capi
     return isinstance(v, _capi.DeviceBuffer) or bool(getattr(v, 'is_cuda', False))
+
+
+def _open_label_source(seg):
+    """the segmentation of full_roi_inference / evaluate_substacks: a resident label volume, or a
+    host array-like / 'npy://file'.  Apart from `_open_source`: a device tensor here is labels,
+    never grayscale."""
+    if isinstance(seg, (_DeviceLabelSource, _ArraySource)):
+        return seg
+    if _is_device_volume(seg):
+        return _DeviceLabelSource(seg)
+    if isinstance(seg, str):
+        if seg.startswith('npy://'):
+            return _ArraySource(np.load(seg[6:], mmap_mode='r'))
+        raise NotImplementedError(
+            'segmentation source %r needs a labelmap reader, which is not installed; pass an '
+            "array, a device-resident volume or 'npy://file'" % (seg,))
+    return _ArraySource(seg)
+
+
+def _resident_cap_bytes():
+    """FPL_PIPE_RESIDENT_GB (default 64; 0: never) in bytes"""
+    return float(os.environ.get('FPL_PIPE_RESIDENT_GB', '64')) * 2 ** 30
+
+
+def _labels_fit(extent, itemsize, gray_bytes, cap_bytes):
+    """whether a host label volume goes to the GPU: its bytes and the `gray_bytes` of grayscale
+    this call has uploaded stay together within the cap"""
+    nbytes = int(np.prod([int(e) for e in extent], dtype=object)) * int(itemsize)
+    return 0 < nbytes and nbytes + int(gray_bytes) <= cap_bytes
+
+
+def _label_points(locs, extent):
+    """(n, 3) int64 (z, y, x) of (x, y, z) locations: rounded (numpy's half to even) and
+    clipped into the volume"""
+    return np.clip(np.round(locs).astype(np.int64)[:, ::-1], 0, np.asarray(extent) - 1)
 
 
 def _open_source(data_source):
@@ -282,11 +371,10 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
     labels are read from it at the rounded locations, else all labels are equal."""
     # the reference reads a 'segmentation' labelmap from a second DVID node
     # (dvid_seg_info = [server, uuid]); here it is a label volume with the image's
-    # extents: array-like or 'npy://file'
+    # extents: array-like, 'npy://file', or a volume already resident on the GPU
     seg_src = None
     if dvid_seg_info is not None:
-        seg_src = _open_source(dvid_seg_info)
-        assert isinstance(seg_src, _ArraySource), 'the segmentation must be an array source'
+        seg_src = _open_label_source(dvid_seg_info)
     for d in (working_dir, '%s/norm' % working_dir):
         os.makedirs(d, exist_ok=True)
     norm_dir = '%s/norm' % working_dir
@@ -321,19 +409,34 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
     # copy each) and uploading them one by one costs more than the inference.  FPL_PIPE_RESIDENT_GB (default 64;
     # 0: never) bounds the size; larger volumes keep the host path (cut + upload per substack, prefetched).
     uploaded = None
+    gray_bytes = 0
     if isinstance(src, _ArraySource) and mine and np.dtype(src.arr.dtype) == np.uint8:
-        cap = float(os.environ.get('FPL_PIPE_RESIDENT_GB', '64')) * 2 ** 30
+        cap = _resident_cap_bytes()
         nbytes = int(np.prod(src.extent))
         if 0 < nbytes <= cap:
             uploaded = prog0.ctx.malloc(src.extent, np.uint8)
-            plane = int(src.extent[1]) * int(src.extent[2])
-            step = max(1, (256 << 20) // max(plane, 1))            # 256 MiB slabs: a memmap is read as it goes
-            for z0 in range(0, src.extent[0], step):
-                z1 = min(src.extent[0], z0 + step)
-                part = np.ascontiguousarray(src.arr[z0:z1])
-                prog0.ctx.memcpy(uploaded.ptr + z0 * plane, part, part.nbytes)
-            prog0.ctx.synchronize()
+            try:
+                plane = int(src.extent[1]) * int(src.extent[2])
+                step = max(1, (256 << 20) // max(plane, 1))            # 256 MiB slabs: a memmap is read as it goes
+                for z0 in range(0, src.extent[0], step):
+                    z1 = min(src.extent[0], z0 + step)
+                    part = np.ascontiguousarray(src.arr[z0:z1])
+                    prog0.ctx.memcpy(uploaded.ptr + z0 * plane, part, part.nbytes)
+                prog0.ctx.synchronize()
+            except BaseException:
+                uploaded.free()
+                raise
             src = _DeviceSource(uploaded)
+            gray_bytes = nbytes
+    # The labels likewise: a resident label volume is read where it lies - voxel2obj fills its padded segmentation
+    # from the substack's box of it (seg_origin), no label cube is cut - and a host volume joins the grayscale on
+    # the GPU when both together stay within the cap (the cube of 8-byte labels is eight times the grayscale's:
+    # a strided 1.5 GB host copy and as large an upload per 582^3 substack); else the host path cuts and uploads.
+    seg_res = seg_src if isinstance(seg_src, _DeviceLabelSource) else None
+    seg_uploaded = None
+    if seg_res is not None:
+        assert seg_res.device == dev, \
+            'the segmentation lives on GPU %d, the network on GPU %d' % (seg_res.device, dev)
     # Lanes on the GPU.  An inference lane (a host thread + context + copy of the program)
     # prepares and infers its substacks; each has a post-processing lane of its own (a
     # second thread + context: own HIP stream and voxel2obj state) that works on substack
@@ -427,7 +530,10 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
                                       mean=st['mn_use'], std=image_normalize[1],
                                       precision=prec, dst=preds[k % 2], dims=(image_sz,) * 3)
                     seg_kw = {}
-                    if seg_src is not None:           # fri_postprocess, reference :1143-1150
+                    if seg_res is not None:           # fri_postprocess, reference :1143-1150
+                        seg_kw = dict(seg=seg_res.vol, seg_origin=origin, seg_dilate=8,
+                                      seg_sz_thd=5000, seg_force=10)
+                    elif seg_src is not None:
                         seg_dt = seg_src.arr.dtype if seg_src.arr.dtype.itemsize in (4, 8) \
                             else np.uint64
                         seg_kw = dict(seg=seg_src.cube_host(origin, image_sz, seg_dt), seg_dilate=8,
@@ -450,15 +556,24 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
             if lane != 0:
                 prog.close()
 
-    lanes = [threading.Thread(target=run_lane, args=(l, mine[l::n_lanes]))
-             for l in range(1, n_lanes)]
-    for t in lanes:
-        t.start()
-    run_lane(0, mine[0::n_lanes])
-    for t in lanes:
-        t.join()
-    if uploaded is not None:
-        uploaded.free()
+    try:
+        if isinstance(seg_src, _ArraySource) and mine:
+            dt = np.dtype(seg_src.arr.dtype)
+            itemsize = dt.itemsize if dt.kind in 'iu' and dt.itemsize in (4, 8) else 8
+            if _labels_fit(seg_src.extent, itemsize, gray_bytes, _resident_cap_bytes()):
+                seg_res = seg_uploaded = _DeviceLabelSource.upload(prog0.ctx, seg_src)
+        lanes = [threading.Thread(target=run_lane, args=(l, mine[l::n_lanes]))
+                 for l in range(1, n_lanes)]
+        for t in lanes:
+            t.start()
+        run_lane(0, mine[0::n_lanes])
+        for t in lanes:
+            t.join()
+    finally:                                        # whatever went up comes down, on failure too
+        if seg_uploaded is not None:
+            seg_uploaded.free()
+        if uploaded is not None:
+            uploaded.free()
     if failure:
         raise failure[0]
     if timings is not None:
@@ -503,14 +618,18 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
 
 def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse', device=None):
     """the point list with the duplicates along substack borders merged: rm_tbar_multi_pred and
-    merge_multi_pred.  `seg_src`, an array source of segment ids with the image's extents,
-    gives the points' labels at their rounded (x, y, z), clipped into the volume."""
+    merge_multi_pred.  `seg_src`, a source of segment ids with the image's extents (a host array
+    source or a resident label volume), gives the points' labels at their rounded (x, y, z),
+    clipped into the volume; the coordinates are prepared on the host either way."""
     from . import fplsynapses
     labels = None
     if seg_src is not None and len(tbars['conf']):
-        at = np.clip(np.round(tbars['locs']).astype(np.int64)[:, ::-1], 0,
-                     np.asarray(seg_src.extent) - 1)
-        labels = np.asarray(seg_src.arr[at[:, 0], at[:, 1], at[:, 2]])
+        at = _label_points(tbars['locs'], seg_src.extent)
+        if isinstance(seg_src, _DeviceLabelSource):
+            from . import runtime
+            labels = seg_src.labels_at(runtime.get_context(seg_src.device), at)
+        else:
+            labels = np.asarray(seg_src.arr[at[:, 0], at[:, 1], at[:, 2]])
     found = fplsynapses.rm_tbar_multi_pred(tbars, neighbor_thresh=neighbor_thresh, labels=labels,
                                            method=method, device=device)
     return fplsynapses.merge_multi_pred(tbars, *found)

@@ -38,12 +38,19 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define FPL_ABI_VERSION 8
+#define FPL_ABI_VERSION 9
 
 typedef struct fpl_ctx fpl_ctx;
 typedef struct fpl_program fpl_program;
 
-enum fpl_mem { FPL_MEM_HOST = 0, FPL_MEM_DEVICE = 1 };
+enum fpl_mem { FPL_MEM_HOST = 0, FPL_MEM_DEVICE = 1,
+               FPL_MEM_DEVICE_BOX = 2 /* fpl_v2o_set_seg only: a box of a resident volume */ };
+/* what fpl_v2o_set_seg reads with FPL_MEM_DEVICE_BOX */
+typedef struct fpl_seg_box {
+  const void *vol;     /* device pointer: (Z,Y,X) labels, 4 or 8 bytes each */
+  int64_t extent[3];   /* of the volume */
+  int64_t origin[3];   /* of the prediction's box in it; may be negative */
+} fpl_seg_box;
 enum fpl_dtype { FPL_U8 = 0, FPL_F32 = 1, FPL_F64 = 2 };
 /* arithmetic of the convolutions: fp32 (exact reference arithmetic), or 16-bit MFMA
  * operands with fp32 accumulation - bfloat16 (8 significant bits), IEEE half (11
@@ -210,6 +217,13 @@ int fpl_v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
  * to four 64-bit words; <= 31 - one word, every caller of the reference uses 27 - runs from LDS). */
 int fpl_v2o_set_seg(fpl_ctx *ctx, const void *seg, int32_t seg_bytes, int seg_mem,
                     const int64_t dims[3], int64_t sz_thd);
+/* seg_mem = FPL_MEM_DEVICE_BOX: `seg` points to a HOST fpl_seg_box that describes a label volume
+ * RESIDENT in device memory - (Z,Y,X), extents `extent`, seg_bytes per label - of which the box
+ * origin .. origin + dims is the prediction's.  One kernel fills the padded segmentation from the
+ * volume: no cube is cut, nothing is allocated for it.  The box may reach outside the volume or
+ * miss it altogether: labels there are 0, as fri_get_image pads the grayscale
+ * (fplobjdetect.py:1044-1070); coordinates as for fpl_crop_substack_u8.  Everything after the
+ * fill is the same. */
 int fpl_v2o_select(fpl_ctx *ctx, const int64_t *ranks, int32_t n_ranks, float *rank_values);
 int fpl_v2o_nms_seg(fpl_ctx *ctx, double thresh, int32_t seg_dilate, int32_t seg_force,
                     double *out_zyxv, int64_t cap, int64_t *n_out, int32_t *n_rounds);

@@ -720,6 +720,11 @@ def main():
                     help="roi: 'synth' generates every substack + buffer on the device inside the timed "
                          "region (the stand-in for the reference's DVID fetch); 'resident' keeps the whole "
                          "volume in HBM (generated before the clock starts) and cuts the substacks out of it")
+    ap.add_argument('--roi-seg', default='none', choices=['none', 'host', 'resident'],
+                    help="roi: run the segmentation-aware post-processing on a synthetic label volume (blocks of "
+                         "32^3 hashed to 8-byte ids): 'host' hands it over as a host array and keeps it there "
+                         "(FPL_PIPE_RESIDENT_GB=0: a label cube is cut and uploaded per substack), 'resident' as "
+                         "a device tensor; the CPU oracle check is skipped (it takes minutes per substack)")
     ap.add_argument('--skip-oracle', action='store_true',
                     help='roi: do not re-derive one substack on the CPU oracle (for traces)')
     ap.add_argument('--dedupe-reps', type=int, default=5)
@@ -994,20 +999,37 @@ def main():
             ctx.synth_volume_u8(5, (n, n, n), out=resident)
             torch.cuda.synchronize()
             src = resident
-        fplobjdetect.full_roi_inference(src, None, roi[:6], net, 0.1, wd + '/warm', norm)
+        seg_kw = {}
+        if a.roi_seg != 'none':
+            # blocks of (z // 32, y // 32, x // 32) hashed to 8-byte ids, made on the device plane by plane
+            labels = torch.empty((n, n, n), dtype=torch.int64, device='cuda')
+            ax = torch.arange(n, dtype=torch.int64, device='cuda') // 32
+            plane = (ax[:, None] * 19349663) ^ (ax[None, :] * 83492791)
+            for bz in range(0, n, 32):
+                labels[bz:bz + 32] = (((plane ^ (bz // 32 * 73856093)) + 1) * -7046029254386353131)[None]
+            torch.cuda.synchronize()
+            if a.roi_seg == 'host':
+                host_labels = labels.cpu().numpy().view(np.uint64)
+                del labels
+                torch.cuda.empty_cache()
+                os.environ['FPL_PIPE_RESIDENT_GB'] = '0'
+                seg_kw = dict(dvid_seg_info=host_labels)
+            else:
+                seg_kw = dict(dvid_seg_info=labels)
+        fplobjdetect.full_roi_inference(src, None, roi[:6], net, 0.1, wd + '/warm', norm, **seg_kw)
         ctx.timing(True); ctx.timing_reset()
         t0 = time.perf_counter()
         out = fplobjdetect.full_roi_inference(src, None, wd + '/roi_00.txt', net, 0.1,
-                                              wd + '/work', norm)
+                                              wd + '/work', norm, **seg_kw)
         dt = time.perf_counter() - t0
         # (lane 0's inference kernels only: HIP events on the six concurrent streams of the pipeline time the
         # waits for one another, not execution - the kernel table of ALL lanes is the rocprofv3 kernel trace of
         # this run, profiles/r05_roi1536_kernel_stats.csv)
         kern = {k: round(v['ms'], 2) for k, v in ctx.timing_get().items()}
         ctx.timing(False)
-        if a.skip_oracle:
-            print(json.dumps(dict(substacks=len(roi), seconds=dt, mvox_s=n ** 3 / dt / 1e6,
-                                  detections=int(len(out['conf'])))), flush=True)
+        if a.skip_oracle or a.roi_seg != 'none':
+            print(json.dumps(dict(substacks=len(roi), seconds=dt, mvox_s=n ** 3 / dt / 1e6, seg=a.roi_seg,
+                                  source=a.roi_source, detections=int(len(out['conf'])))), flush=True)
             shutil.rmtree(wd, ignore_errors=True)
             return
         # one substack re-derived and post-processed by the CPU oracle
