@@ -39,6 +39,11 @@ LABEL_LIBRARIES is a sixth table of that shape, for reads of a resident label vo
 gathers the labels of points and pads a box of the volume.  EVERY_LIBRARY is pinned as well, so
 BUILT_LIBRARIES is what build() walks.  Its source shares csrc/seg_box.h with libfplhip.so, so
 the headers of csrc/ are part of its stamp.
+
+MERGE_LIBRARIES is a seventh table of that shape, beside POST_LIBRARIES: libfplmerge.so runs the
+merge loop of rm_tbar_multi_pred on the neighbour table libfplnear.so leaves on the device
+(solver='device').  BUILT_LIBRARIES is pinned too, so LIBRARIES, the union of all seven, is what
+build() walks now.
 """
 import argparse
 import hashlib
@@ -77,6 +82,10 @@ LABEL_LIBRARIES = (
     ('seg', 'seg', 'fpls', 'fplseg.h', 'libfplseg.so'),                # labels of a resident volume
 )
 BUILT_LIBRARIES = EVERY_LIBRARY + LABEL_LIBRARIES
+MERGE_LIBRARIES = (
+    ('merge', 'merge', 'fplg', 'fplmerge.h', 'libfplmerge.so'),        # rm_tbar_multi_pred's merge loop
+)
+LIBRARIES = BUILT_LIBRARIES + MERGE_LIBRARIES
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -194,16 +203,16 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in BUILT_LIBRARIES:
+    for row in LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
     """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
-    SOLVE_LIBRARIES or LABEL_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the
-    row's prefix only"""
-    row = next(r for r in BUILT_LIBRARIES if r[0] == key)
+    SOLVE_LIBRARIES, LABEL_LIBRARIES or MERGE_LIBRARIES: same flags, same SHA-stamped rebuild, a
+    version script that exports the row's prefix only"""
+    row = next(r for r in LIBRARIES if r[0] == key)
     _, sub, prefix, header, lib = row
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])

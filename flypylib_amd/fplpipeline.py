@@ -356,7 +356,8 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
                        roi_force_file=False,
                        instance_name='grayscale',
                        dvid_seg_info=None, precision=None, timings=None,
-                       neighbor_thresh=None, merge_method='sparse', merge_device=None):
+                       neighbor_thresh=None, merge_method='sparse', merge_device=None,
+                       merge_solver='host'):
     """Predictions of a trained network within the substacks of an ROI, cached per
     substack in `working_dir` (reference :841-986; same arguments).  `dvid_roi` is
     an ROI text file (`roi_from_txt`) or a list of `szyx`; `precision` overrides the
@@ -365,8 +366,8 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
 
     neighbor_thresh=None (default): nothing more.  With a number, the rank that writes `all.p`
     then merges the detections two neighbouring substacks both made of one T-bar
-    (fplsynapses.rm_tbar_multi_pred with method=`merge_method`, device=`merge_device`, and
-    merge_multi_pred), writes the merged list to `all_merged.p` beside it and returns it; the
+    (fplsynapses.rm_tbar_multi_pred with method=`merge_method`, device=`merge_device`,
+    solver=`merge_solver` - 'device' runs the merge loop on the GPU too - and merge_multi_pred), writes the merged list to `all_merged.p` beside it and returns it; the
     other ranks return the unmerged list.  With a segmentation (`dvid_seg_info`) the points'
     labels are read from it at the rounded locations, else all labels are equal."""
     # the reference reads a 'segmentation' labelmap from a second DVID node
@@ -610,17 +611,20 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
         with open('%s/all.p' % working_dir, 'wb') as f_out:
             pickle.dump(obj, f_out)
         if neighbor_thresh is not None:
-            obj = merge_border_duplicates(obj, neighbor_thresh, seg_src, merge_method, merge_device)
+            obj = merge_border_duplicates(obj, neighbor_thresh, seg_src, merge_method, merge_device,
+                                          merge_solver)
             with open('%s/all_merged.p' % working_dir, 'wb') as f_out:
                 pickle.dump(obj, f_out)
     return obj
 
 
-def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse', device=None):
+def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse', device=None,
+                            solver='host'):
     """the point list with the duplicates along substack borders merged: rm_tbar_multi_pred and
     merge_multi_pred.  `seg_src`, a source of segment ids with the image's extents (a host array
     source or a resident label volume), gives the points' labels at their rounded (x, y, z),
-    clipped into the volume; the coordinates are prepared on the host either way."""
+    clipped into the volume; the coordinates are prepared on the host either way.  `solver` is
+    rm_tbar_multi_pred's: 'device' runs the merge loop on the GPU as well."""
     from . import fplsynapses
     labels = None
     if seg_src is not None and len(tbars['conf']):
@@ -631,7 +635,7 @@ def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse
         else:
             labels = np.asarray(seg_src.arr[at[:, 0], at[:, 1], at[:, 2]])
     found = fplsynapses.rm_tbar_multi_pred(tbars, neighbor_thresh=neighbor_thresh, labels=labels,
-                                           method=method, device=device)
+                                           method=method, device=device, solver=solver)
     return fplsynapses.merge_multi_pred(tbars, *found)
 
 

@@ -213,17 +213,10 @@ def _multi_pred_dense(pos, conf, ll, neighbor_thresh):
     return rm_idx, mv_idx, mv_loc
 
 
-def _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device):
-    """the same loop on the neighbour table of near.py and a host cell grid: no N x N object"""
-    from . import near
+def _sparse_rows(pos, indptr, indices, neighbor_thresh):
+    """the neighbour table, a superset (s <= T2), cut down to what the reference's own expression
+    keeps -> (has_neighbor, indptr, indices)"""
     n = pos.shape[0]
-    if n == 0:
-        return np.zeros(0, 'bool'), np.zeros(0, 'bool'), np.zeros(pos.shape, 'int')
-    if device is None:
-        indptr, indices = near.pairs_numpy(pos, neighbor_thresh)
-    else:
-        indptr, indices = near.pairs_device(pos, neighbor_thresh, device)
-    # the table is a superset (s <= T2): keep what the reference's own expression keeps
     keep = np.zeros(len(indices), bool)
     owner = np.repeat(np.arange(n), np.diff(indptr))
     step = 1 << 20
@@ -234,7 +227,61 @@ def _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device):
     indices = indices[keep]
     indptr = np.zeros(n + 1, np.int64)
     np.cumsum(has_neighbor, out=indptr[1:])
-    del owner, keep
+    return has_neighbor, indptr, indices
+
+
+def _merge_visit(ii, row, pos, conf, ll, neighbor_thresh, grid, rm_idx, mv_idx, mv_loc, watch=None):
+    """one visit of the reference loop: point `ii`, not removed, with the filtered row `row` of
+    the neighbour table.  `watch`, if given, is called with the points of every ball that pass
+    the distance and label tests, removed or not - the closure of dedupe.py listens there."""
+    jj = row[(ll[row] == ll[ii]) & np.logical_not(rm_idx[row])]
+
+    if jj.size > 0:
+        mv_idx[ii] = True
+
+        old_loc = pos[ii, :]
+        at = np.searchsorted(jj, ii)
+        cand = np.concatenate([jj[:at], [ii], jj[at:]])      # ascending, ii among them
+        while True:
+            # new location by interpolation, over the candidates alone, in index order
+            if cand.size:
+                ww = conf[cand]
+                ww = ww / np.sum(ww)
+                rows = ww.reshape((-1, 1)) * pos[cand]
+                mean = rows[0]
+                for r in rows[1:]:
+                    mean = mean + r
+            else:
+                mean = np.full(3, np.nan)        # the reference's 0 / 0
+            mv_loc[ii, :] = np.round(mean)
+            if np.array_equal(old_loc, mv_loc[ii, :]):
+                break
+
+            old_loc = mv_loc[ii, :].copy()
+            # a ball around the moved centre may hold points that are partners of no
+            # candidate: asked of the grid, not of the table
+            ball = grid.ball(mv_loc[ii, :])
+            new_dists = np.sqrt(np.sum(
+                (pos[ball] - mv_loc[ii, :]) ** 2, axis=1))
+            near_same = (new_dists < neighbor_thresh) & (ll[ball] == ll[ii])
+            if watch is not None:
+                watch(ball[near_same])
+            cand = ball[near_same & (np.logical_not(rm_idx[ball]))]
+
+        rm_idx[cand] = True
+
+
+def _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device):
+    """the same loop on the neighbour table of near.py and a host cell grid: no N x N object"""
+    from . import near
+    n = pos.shape[0]
+    if n == 0:
+        return np.zeros(0, 'bool'), np.zeros(0, 'bool'), np.zeros(pos.shape, 'int')
+    if device is None:
+        indptr, indices = near.pairs_numpy(pos, neighbor_thresh)
+    else:
+        indptr, indices = near.pairs_device(pos, neighbor_thresh, device)
+    has_neighbor, indptr, indices = _sparse_rows(pos, indptr, indices, neighbor_thresh)
     grid = near.CellGrid(pos, neighbor_thresh)
 
     tt_idx = np.argsort(-conf)
@@ -246,50 +293,20 @@ def _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device):
     for ii in tt_idx[has_neighbor[tt_idx] > 0]:
         if rm_idx[ii]:
             continue
-
-        row = indices[indptr[ii]:indptr[ii + 1]]
-        jj = row[(ll[row] == ll[ii]) & np.logical_not(rm_idx[row])]
-
-        if jj.size > 0:
-            mv_idx[ii] = True
-
-            old_loc = pos[ii, :]
-            at = np.searchsorted(jj, ii)
-            cand = np.concatenate([jj[:at], [ii], jj[at:]])      # ascending, ii among them
-            while True:
-                # new location by interpolation, over the candidates alone, in index order
-                if cand.size:
-                    ww = conf[cand]
-                    ww = ww / np.sum(ww)
-                    rows = ww.reshape((-1, 1)) * pos[cand]
-                    mean = rows[0]
-                    for r in rows[1:]:
-                        mean = mean + r
-                else:
-                    mean = np.full(3, np.nan)        # the reference's 0 / 0
-                mv_loc[ii, :] = np.round(mean)
-                if np.array_equal(old_loc, mv_loc[ii, :]):
-                    break
-
-                old_loc = mv_loc[ii, :].copy()
-                # a ball around the moved centre may hold points that are partners of no
-                # candidate: asked of the grid, not of the table
-                ball = grid.ball(mv_loc[ii, :])
-                new_dists = np.sqrt(np.sum(
-                    (pos[ball] - mv_loc[ii, :]) ** 2, axis=1))
-                cand = ball[(new_dists < neighbor_thresh) &
-                            (ll[ball] == ll[ii]) &
-                            (np.logical_not(rm_idx[ball]))]
-
-            rm_idx[cand] = True
+        _merge_visit(ii, indices[indptr[ii]:indptr[ii + 1]], pos, conf, ll, neighbor_thresh, grid,
+                     rm_idx, mv_idx, mv_loc)
 
     rm_idx[mv_idx] = False
 
     return rm_idx, mv_idx, mv_loc
 
 
+SOLVER_FORMS = ("solver='host' (default: the loop on the host, any method and device=) or "
+                "solver='device' (with method='sparse' and device=<int> or True: the loop on the GPU)")
+
+
 def rm_tbar_multi_pred(tbars_in, dvid_node=None, segm_name=None, neighbor_thresh=30, labels=None,
-                       method='dense', device=None):
+                       method='dense', device=None, solver='host', info=None):
     """Detections of one T-bar made twice, by two neighbouring substacks (reference :378-449).
     In order of falling confidence, a point that has not been removed gathers the points of
     its own segment closer than `neighbor_thresh`, moves to their confidence-weighted mean
@@ -321,14 +338,35 @@ def rm_tbar_multi_pred(tbars_in, dvid_node=None, segm_name=None, neighbor_thresh
 
     device=<int> (or True, the runtime's default device), with method='sparse' only, takes the
     table from libfplnear.so (near.pairs_device: the same bytes); device=None builds it on the
-    host.  No host fallback: a missing library raises.  Anything else is a ValueError."""
+    host.  No host fallback: a missing library raises.  Anything else is a ValueError.
+
+    solver='host' (default) runs the loop itself on the host, as above.  solver='device', with
+    method='sparse' and device= only, runs it on the GPU with libfplmerge.so (dedupe.merge_device):
+    the table stays on the device, the loop runs per connected component of it, a lane each, and
+    the components whose run met something it cannot reproduce exactly - a point of another
+    component in a ball, more than 7 candidates, an empty candidate set, a point that does not
+    come to rest, a large component - are run again on the host, in the global order.  The three
+    arrays are those of method='sparse', bit for bit.  It asks for float64 confidences and
+    float64 locations (integer locations up to 2^24 in magnitude are taken as float64, which is
+    exact); anything else is a ValueError that names solver='host'.  A missing library raises
+    FplMergeError before a missing GPU is reported; the host loop is never substituted.
+    `info`, a dict, then receives `components`, `largest`, `sweeps`, `host_components`,
+    `host_points` and `closure_rounds` (dedupe.py says what each counts)."""
     if method not in ('dense', 'sparse'):
         raise ValueError("method %r: 'dense' (the reference's matrix) or 'sparse'" % (method,))
     if device is not None and method != 'sparse':
         raise ValueError("device=%r needs method='sparse': the dense method is the host "
                          'specification' % (device,))
+    if solver not in ('host', 'device'):
+        raise ValueError('solver %r: %s' % (solver, SOLVER_FORMS))
+    if solver == 'device' and (method != 'sparse' or device is None):
+        raise ValueError("solver='device' with method=%r, device=%r: %s"
+                         % (method, device, SOLVER_FORMS))
     ll = _multi_pred_labels(tbars_in, segm_name, labels)
     pos, conf = tbars_in['locs'], tbars_in['conf']
+    if solver == 'device':
+        from . import dedupe
+        return dedupe.merge_device(pos, conf, ll, neighbor_thresh, device, info=info)
     if method == 'dense':
         return _multi_pred_dense(pos, conf, ll, neighbor_thresh)
     return _multi_pred_sparse(pos, conf, ll, neighbor_thresh, device)

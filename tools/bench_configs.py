@@ -585,6 +585,36 @@ def dedupe_bench(ctx, torch, sizes=(3000, 100000, 1000000), reps=5):
                                                    device=ctx.device), call_reps)
         row['equal_results'] = bool(all(np.array_equal(a, b) for a, b in zip(r_host, r_dev)))
         row['moved'], row['removed'] = int(r_host[1].sum()), int(r_host[0].sum())
+        # solver='device': the merge loop on the GPU too, same process, same inputs
+        from flypylib_amd import dedupe
+        minfo = {}
+        row['solver_device_ms'], r_solv = timed(
+            lambda: fplsynapses.rm_tbar_multi_pred(tb, neighbor_thresh=thresh, method='sparse',
+                                                   device=ctx.device, solver='device', info=minfo),
+            call_reps, warm=1)
+        row['solver_device_equal'] = bool(all(np.array_equal(a, b) and a.dtype == b.dtype
+                                              for a, b in zip(r_host, r_solv)))
+        row['solver_device_info'] = dict(minfo)
+        row['solver_device_to_call_sparse_device'] = (row['solver_device_ms']['median']
+                                                      / row['call_sparse_device_ms']['median'])
+        stage_runs = []
+        for _ in range(call_reps):
+            st = {}
+            r_st = dedupe.merge_device(tb['locs'], tb['conf'], np.zeros(n), thresh, ctx.device, stages=st)
+            row['solver_device_equal'] &= bool(all(np.array_equal(a, b) for a, b in zip(r_host, r_st)))
+            stage_runs.append(st)
+        row['solver_device_stages_ms'] = {k: spread([s[k] for s in stage_runs]) for k in stage_runs[0]}
+        row['solver_device_stages_timing'] = (
+            'wall clock per stage, synchronised after each (which the plain call does not do): '
+            'argsort_upload = np.argsort(-conf), its rank and the uploads of conf, labels, rank; '
+            'table = upload of the points, cell keys, sort, count, fill; filter = the rows the '
+            'reference keeps; labels = the sweeps (solver_device_info.sweeps of them, a read-back '
+            'each); sort = group keys, torch.sort, boundaries, compaction; solve = the merge loop '
+            'and the compaction of the flagged ids; download = rm, mv, mv_loc and, if a component '
+            'was flagged, what the closure reads; closure_host = the host loop over the flagged '
+            'components')
+        points_with_neighbours = int((np.diff(near.pairs_numpy(pts, thresh)[0]) > 0).sum())
+        row['solver_device_host_share'] = minfo['host_points'] / max(points_with_neighbours, 1)
         if n <= 5000:
             row['call_dense_ms'], r_dense = timed(
                 lambda: fplsynapses.rm_tbar_multi_pred(tb, neighbor_thresh=thresh, method='dense'), reps)
