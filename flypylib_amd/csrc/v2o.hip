@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "seg_box.h"
+#include "v2o_plan.h"     // every dispatch condition and tile constant of this file
 
 // The smoothing must round every product and every sum on its own, as scipy's C does on
 // x86-64.  hipcc's default for device code fuses a * b + c into v_fma_f64 across
@@ -37,8 +38,6 @@ namespace {
 
 __device__ __forceinline__ double mul_rn(double a, double b) { return a * b; }
 __device__ __forceinline__ double add_rn(double a, double b) { return a + b; }
-
-constexpr int CELL = 4;
 
 __device__ __forceinline__ int64_t reflect_idx(int64_t i, int64_t n) {
   const int64_t p = 2 * n;
@@ -171,8 +170,7 @@ __global__ __launch_bounds__(256) void gauss_pass_win(
 // row segment + 2*WR halo (reflected at the row ends) is loaded coalesced once, a
 // thread then reads its 4 + 2*WR inputs as aligned 16-B LDS pieces - one global
 // load per input instead of (4 + 2*WR) / 4 strided ones.  Arithmetic as gauss_pass;
-// the outer r shell is zeroed on store.
-constexpr int GX_ROWS = 8, GX_SEG = 128;
+// the outer r shell is zeroed on store.  (GX_ROWS, GX_SEG: v2o_plan.h)
 // first radix level of the order statistics: the top L0_BITS key bits, histogrammed by
 // the last smoothing pass (10 bits = 4 KiB of LDS: three workgroups of the fused pass
 // per CU)
@@ -277,8 +275,8 @@ __global__ __launch_bounds__(256) void gauss_x_lds(
 
 // (rounds 2 - 3 ran the z pass as a register-window kernel, gauss_z_win: every thread re-read
 // its 2 WR halo, 2.7 x the volume through L2; the ring form below replaced it in round 4 -
-// bit-identical, 0.546 -> 0.522 ms at 582^3 - and the window kernel was removed in round 5)
-constexpr int GZ_OUT = 12;       // (the size limit of the 32-bit offsets below still counts in these rows)
+// bit-identical, 0.546 -> 0.522 ms at 582^3 - and the window kernel was removed in round 5;
+// GZ_OUT in v2o_plan.h is what is left of it)
 
 // z pass, ring form (round 4): a thread walks a SEGMENT of its (y, x) column, 2 WR outputs at a
 // time, with the 4 WR inputs they need in registers as two halves; after a step the upper half is
@@ -373,9 +371,7 @@ __global__ __launch_bounds__(512) void gauss_z_ring(
 // 4 B/voxel write and one read less); arithmetic and rounding points are unchanged.
 // The 1-D grid is decoded so that the blocks an XCD receives (b, b + 8, ...) walk the
 // y tiles of consecutive planes: y neighbours share their 2*WR halo rows in that L2.
-// 12 rows: the tile is 33 KiB at P2 = 636 and four workgroups fit a CU (16 rows, three
-// workgroups: 1.07 ms against 0.94; 8 rows: 0.97).
-constexpr int GYX_TY = 12;
+// (GYX_TY rows per tile, the tile row and the LDS it takes: v2o_plan.h)
 
 template <int WR>
 __global__ __launch_bounds__(512) void gauss_yx_fused(
@@ -542,32 +538,6 @@ __global__ __launch_bounds__(512) void gauss_yx_fused(
       if (lh[b]) atomicAdd(&hist0[b], (unsigned long long)lh[b]);
 }
 
-// LDS floats per tile row of gauss_yx_fused: the row, its two halos, rounded up to a
-// 16-B multiple plus 4 (the last thread's aligned window may read 3 floats past it)
-static inline int gyx_lrow(int64_t P2, int wr) {
-  return (int)((ceil_div64(P2, 8) * 8 + 2 * wr + 3) / 4 * 4 + 4);
-}
-// workgroup size (a multiple of 64 in [256, 512]) that wastes the fewest lanes on `n`
-// columns / pieces per pass
-static inline int best_block(int64_t n) {
-  int best = 256;
-  double waste = 1e9;
-  for (int bd = 256; bd <= 512; bd += 64) {
-    const double wst = (double)(ceil_div64(n, bd) * bd) / (double)n;
-    if (wst < waste - 1e-9) { waste = wst; best = bd; }
-  }
-  return best;
-}
-static inline size_t gyx_lds_bytes(int64_t P2, int wr) {
-  return (size_t)GYX_TY * gyx_lrow(P2, wr) * sizeof(float) +
-         (size_t)(GYX_TY / CELL) * ceil_div64(P2, CELL) * sizeof(unsigned long long);
-}
-static inline bool gyx_fits(const int64_t P[3], int wr) {
-  // single-bounce reflections, 32-bit in-plane offsets, tile + cell keys within 60 KiB
-  return P[1] * P[2] * 4 < ((int64_t)1 << 31) && P[2] >= 2 * wr && P[1] >= GYX_TY + 2 * wr && P[0] * ceil_div64(P[1], GYX_TY) < (1 << 28) &&
-         gyx_lds_bytes(P[2], wr) <= 60 * 1024;
-}
-
 // Compaction without global atomics: workgroup b scans elements [b*chunk, (b+1)*chunk)
 // and packs those whose key matches (key & mask) == want to the front of the same
 // range of `list` (as floats); counts[b] = how many.
@@ -634,64 +604,46 @@ __global__ __launch_bounds__(256) void key_histogram_chunks(
 
 template <int WR>
 int launch_gauss_win(fpl_ctx *ctx, PadView pv, float *a, float *b, const int64_t P[3],
-                     const double *w_dev, int r, unsigned long long *hist0,
-                     unsigned long long *cellmax, float floor_v, bool *cellmax_done) {
+                     const V2oSmoothPlan &plan, const double *w_dev, int r,
+                     unsigned long long *hist0, unsigned long long *cellmax, float floor_v,
+                     bool *cellmax_done) {
   *cellmax_done = false;
   hipStream_t st = ctx->stream;
-  constexpr int OUT_ZY = 16;                 // outputs per thread of gauss_pass_win<0/1>
-  const bool fused = gyx_fits(P, WR) && !getenv("FPL_V2O_UNFUSED");
+  const bool fused = plan.fused;
   // fused: z pass -> b, y+x -> a;  separate passes: z -> a, y -> b, x -> a
-  // 32-bit in-column / in-plane offsets of gauss_z_ring
-  const bool small = (GZ_OUT + 2 * WR) * pv.D1 * pv.D2 < ((int64_t)1 << 31) &&
-                     P[1] * P[2] * GZ_OUT < ((int64_t)1 << 31) && P[0] >= 2 * WR;
-  if (small && !getenv("FPL_V2O_UNFUSED")) {
-    // ring form: segments of a multiple of 4 WR outputs (two steps), about a quarter of the column
-    const int bd = best_block(P[2]);
-    const int64_t nxb = ceil_div64(P[2], bd);
-    const int64_t seg_len = std::max<int64_t>(4 * WR, ceil_div64(ceil_div64(P[0], 4), 4 * WR) * 4 * WR);
-    const int64_t nseg = ceil_div64(P[0], seg_len);
-    const int64_t nwork = nxb * nseg * P[1];
+  if (plan.ring) {
+    const int64_t nwork = plan.grid_z(ctx->n_cu);
     FPL_REQUIRE(ctx, nwork < ((int64_t)1 << 31), "voxel2obj: volume too large");
     TimedLaunch tl(ctx, "v2o_gauss_z");
-    gauss_z_ring<WR><<<(unsigned)nwork, bd, 0, st>>>(
-        pv, fused ? b : a, (int)P[0], (int)P[1], (int)P[2], w_dev, (int)nxb, (int)nseg, (int)seg_len);
+    gauss_z_ring<WR><<<(unsigned)nwork, plan.block, 0, st>>>(
+        pv, fused ? b : a, (int)P[0], (int)P[1], (int)P[2], w_dev, (int)plan.nxb, (int)plan.nseg,
+        (int)plan.seg_len);
   } else {
-    const int64_t n = ceil_div64(P[0], OUT_ZY) * P[1] * P[2];
     TimedLaunch tl(ctx, "v2o_gauss_z");
-    gauss_pass_win<0, WR><<<(unsigned)ceil_div64(n, 256), 256, 0, st>>>(
+    gauss_pass_win<0, WR><<<(unsigned)plan.grid_z(ctx->n_cu), 256, 0, st>>>(
         pv, nullptr, fused ? b : a, P[0], P[1], P[2], w_dev, r);
   }
   if (fused) {
-    const int lrow = gyx_lrow(P[2], WR);
-    const size_t lds = gyx_lds_bytes(P[2], WR);
     static bool attr_set[FPL_MAX_DEVICES] = {false};
     if (!attr_set[ctx->device % FPL_MAX_DEVICES]) {
       FPL_HIP(ctx, hipFuncSetAttribute((const void *)gauss_yx_fused<WR>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024));
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, GYX_LDS_MAX));
       attr_set[ctx->device % FPL_MAX_DEVICES] = true;
     }
-    const int64_t nwork = ceil_div64(P[0], CELL) * ceil_div64(P[1], GYX_TY);
-    const int64_t nblk = ceil_div64(nwork, 8) * 8;
-    // phase 1 walks P2 columns, phase 2 16 * ceil(P2 / 8) pieces: size the workgroup
-    // for the columns (the pieces are ~2x as many and split evenly enough)
-    const int bd = best_block(P[2]);
     TimedLaunch tl(ctx, "v2o_gauss_yx");
-    gauss_yx_fused<WR><<<(unsigned)nblk, bd, lds, st>>>(
-        b, a, (int)P[0], (int)P[1], (int)P[2], w_dev, r, lrow, hist0, cellmax,
+    gauss_yx_fused<WR><<<(unsigned)plan.grid_yx(ctx->n_cu), plan.block, plan.lds_bytes, st>>>(
+        b, a, (int)P[0], (int)P[1], (int)P[2], w_dev, r, plan.lrow, hist0, cellmax,
         (int)ceil_div64(P[1], CELL), (int)ceil_div64(P[2], CELL), floor_v);
     *cellmax_done = cellmax != nullptr;
     return 0;
   }
   {
-    const int64_t n = P[0] * ceil_div64(P[1], OUT_ZY) * P[2];
     TimedLaunch tl(ctx, "v2o_gauss_y");
-    gauss_pass_win<1, WR><<<(unsigned)ceil_div64(n, 256), 256, 0, st>>>(pv, a, b, P[0], P[1], P[2], w_dev, r);
+    gauss_pass_win<1, WR><<<(unsigned)plan.grid_y(ctx->n_cu), 256, 0, st>>>(pv, a, b, P[0], P[1], P[2], w_dev, r);
   }
   {
-    const int64_t ntiles = ceil_div64(P[0] * P[1], GX_ROWS) * ceil_div64(P[2], GX_SEG);
-    const int64_t nblk = std::min<int64_t>(ntiles, (int64_t)ctx->n_cu * 8);
     TimedLaunch tl(ctx, "v2o_gauss_x");
-    gauss_x_lds<WR><<<(unsigned)nblk, 256, 0, st>>>(b, a, P[0], P[1], P[2], w_dev, r, hist0);
+    gauss_x_lds<WR><<<(unsigned)plan.grid_x(ctx->n_cu), 256, 0, st>>>(b, a, P[0], P[1], P[2], w_dev, r, hist0);
   }
   return 0;
 }
@@ -874,8 +826,7 @@ __global__ void window_max(const unsigned long long *__restrict__ in,
 // loads the WM_OUTS + 2 HW values once and derives the WM_OUTS window maxima from a shared
 // core plus running suffix / prefix maxima (~4 comparisons per output instead of 2 HW).
 // Work items are ordered so that the blocks of an XCD cover a slab ACROSS the pass axis:
-// no halo is shared between XCDs.
-constexpr int WM_OUTS = 8;
+// no halo is shared between XCDs.  (WM_OUTS: v2o_plan.h)
 
 __device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) {
   return a > b ? a : b;
@@ -1002,10 +953,8 @@ __global__ void pick_winners(const unsigned long long *__restrict__ best,
 // A cleared ball takes voxels from cell c (`dead`: all of them).  Several balls of a round
 // may touch one cell, so the hand-over goes through an exchange: whoever swaps out a LIVE
 // key takes the cell out of the live count and - unless the cell is dead - puts it on the
-// round's re-scan list (once).  Appends are staged in LDS (`stage`, `n_stage`), one global
-// atomic per ball.
-constexpr int CLR_STAGE = 6144;               // >= the 17^3 cells of a bounding box at r = 31;
-                                              // beyond it appends go straight to the list
+// round's re-scan list (once).  Appends are staged in LDS (`stage`, `n_stage`, CLR_STAGE
+// entries - v2o_plan.h - beyond which they go straight to the list), one global atomic per ball.
 __device__ __forceinline__ void touch_cell(unsigned long long *__restrict__ best, int64_t c,
                                            bool dead, unsigned int *stage, unsigned int *n_stage,
                                            unsigned int *n_gone,
@@ -1043,9 +992,7 @@ __device__ __forceinline__ void flush_stage(const unsigned int *stage, unsigned 
 
 // CLR_PARTS workgroups per winner (a round's winners are few and a ball is 82 519 voxels
 // and ~2 500 cells at r = 27: one workgroup per ball left most of the chip idle for the
-// ~90 us a ball takes): clear the r-ball in the live volume
-constexpr int CLR_PARTS = 4;
-constexpr int CLR_ROWS = 1024;                // rows of one part of the cube, r <= 31
+// ~90 us a ball takes): clear the r-ball in the live volume.  (CLR_PARTS, CLR_ROWS: v2o_plan.h)
 __global__ __launch_bounds__(256) void clear_balls(
     const unsigned long long *__restrict__ round_list,
     unsigned long long *__restrict__ counters, float *__restrict__ live,
@@ -1502,13 +1449,10 @@ int fpl_v2o_smooth(fpl_ctx *ctx, const float *pred, int pred_mem,
   FPL_HIP(ctx, hipMemcpyAsync(w_dev, weights + wr, (size_t)(wr + 1) * sizeof(double),
                               hipMemcpyHostToDevice, st));
   PadView pv{pred_dev, dims[0], dims[1], dims[2], r};
-  const unsigned grid = (unsigned)ceil_div64(n_pad, 256);
   // [0..2047] histogram, [2048] compaction counter
   FPL_TRY(tmp.alloc(2049 * sizeof(unsigned long long), &p));
   unsigned long long *hist_dev = (unsigned long long *)p;
   FPL_HIP(ctx, hipMemsetAsync(hist_dev, 0, 2049 * sizeof(unsigned long long), st));
-  // register-window kernels for the kernel radii flypylib's sigmas produce
-  // (sigma 1.5, 2, 3, 5 at truncate 2.0); the plain kernel covers the rest
   // per-cell keys for the NMS, filled by the fused pass
   S.cellmax_valid = false;
   {
@@ -1528,15 +1472,17 @@ int fpl_v2o_smooth(fpl_ctx *ctx, const float *pred, int pred_mem,
   const float floor_v = S.floor > 0.f ? S.floor : 0.f;
   S.floor = 0.f;                         // a floor holds for one smoothing
   S.cellmax_floor = floor_v;
-  bool windowed = true;
-  switch (wr) {
-    case 3: FPL_TRY(launch_gauss_win<3>(ctx, pv, S.smoothed, scratch, P, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
-    case 4: FPL_TRY(launch_gauss_win<4>(ctx, pv, S.smoothed, scratch, P, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
-    case 6: FPL_TRY(launch_gauss_win<6>(ctx, pv, S.smoothed, scratch, P, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
-    case 10: FPL_TRY(launch_gauss_win<10>(ctx, pv, S.smoothed, scratch, P, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
-    default: windowed = false;
+  const V2oSmoothPlan plan = v2o_smooth_plan(P, dims[1], dims[2], wr, getenv("FPL_V2O_UNFUSED") != nullptr);
+  const bool windowed = plan.windowed;
+  switch (windowed ? wr : 0) {
+    case 3: FPL_TRY(launch_gauss_win<3>(ctx, pv, S.smoothed, scratch, P, plan, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
+    case 4: FPL_TRY(launch_gauss_win<4>(ctx, pv, S.smoothed, scratch, P, plan, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
+    case 6: FPL_TRY(launch_gauss_win<6>(ctx, pv, S.smoothed, scratch, P, plan, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
+    case 10: FPL_TRY(launch_gauss_win<10>(ctx, pv, S.smoothed, scratch, P, plan, w_dev, r, hist_dev, S.cellmax, floor_v, &cm_done)); break;
+    default: break;
   }
   if (!windowed) {
+    const unsigned grid = (unsigned)plan.plain_grid;
     {
       TimedLaunch tl(ctx, "v2o_gauss_z");
       gauss_pass<0><<<grid, 256, 0, st>>>(pv, nullptr, S.smoothed, P[0], P[1], P[2],
@@ -1601,13 +1547,13 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
   const int r = S.r;
   hipStream_t st = ctx->stream;
   DevTemp tmp(ctx);
-  const int64_t C0 = ceil_div64(P0, CELL), C1 = ceil_div64(P1, CELL),
-                C2 = ceil_div64(P2, CELL);
-  const int64_t n_cells = C0 * C1 * C2;
+  // (the cells a ball can stage are not counted here: no launch depends on them)
+  const V2oNmsPlan plan = v2o_nms_plan(S.pdims, r, use_seg, getenv("FPL_V2O_WMAX_PLAIN") != nullptr,
+                                       false);
+  const int64_t C0 = plan.C[0], C1 = plan.C[1], C2 = plan.C[2];
+  const int64_t n_cells = plan.n_cells;
   float *live = S.smoothed;
-  // window half-width in cells: cells [c-hw, c+hw] cover [4c-4hw, 4c+4hw+3]
-  // which must contain [p-r, p+r] for every p in [4c, 4c+3]
-  const int hw = (r + CELL - 1) / CELL;
+  const int hw = plan.hw;
   void *p;
   // cell keys: the ones the fused smoothing pass left (consumed here), else a scan
   // (keys taken above a floor are complete only for thresholds >= that floor)
@@ -1632,10 +1578,9 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
   // segmentation-aware suppression with rows wider than 64 voxels: the two row sets of
   // every workgroup's cube live in global memory
   unsigned long long *seg_rows = nullptr;
-  constexpr int SEG_WGS = 1024;
-  if (use_seg && 2 * r + 1 > 64) {
-    const size_t W = (2 * r + 1 + 63) / 64 <= 2 ? 2 : 4;
-    FPL_TRY(tmp.alloc((size_t)SEG_WGS * 2 * (2 * r + 1) * (2 * r + 1) * W * 8, &p));
+  constexpr int SEG_WGS = CLR_SEG_WGS;
+  if (plan.seg_rows_global) {
+    FPL_TRY(tmp.alloc(plan.seg_rows_bytes, &p));
     seg_rows = (unsigned long long *)p;
   }
   FPL_TRY(tmp.alloc(CNT_N * 8, &p));
@@ -1645,7 +1590,7 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
   const unsigned wgrid = (cgrid + 7u) / 8u * 8u;       // window_max: whole XCD rounds
   const unsigned bgrid = std::min<unsigned>(cgrid, (unsigned)ctx->n_cu * 8);   // cell_best: grid-stride
   unsigned long long host_cnt[CNT_N];
-  const bool aligned = P2 % CELL == 0;
+  const bool aligned = plan.aligned;
   // live cells: keys per cell and their count in counters[CNT_LIVE]
   {
     TimedLaunch tl(ctx, "v2o_cell_best");
@@ -1669,9 +1614,7 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
       FPL_HIP(ctx, hipMemsetAsync(counters + CNT_ROUND, 0, 2 * 8, st));
       {
         TimedLaunch tl(ctx, "v2o_window_max");
-        const bool seg_ok = hw >= 1 && hw <= 8 && n_cells < ((int64_t)1 << 31) &&
-                            !getenv("FPL_V2O_WMAX_PLAIN");
-        switch (seg_ok ? hw : 0) {
+        switch (plan.HW) {
           case 1: launch_window_max_seg<1>(st, best, wa, wb, (int)C0, (int)C1, (int)C2, n_cells, counters); break;
           case 2: launch_window_max_seg<2>(st, best, wa, wb, (int)C0, (int)C1, (int)C2, n_cells, counters); break;
           case 3: launch_window_max_seg<3>(st, best, wa, wb, (int)C0, (int)C1, (int)C2, n_cells, counters); break;
@@ -1694,10 +1637,9 @@ static int v2o_nms(fpl_ctx *ctx, double thresh, double *out_zyxv, int64_t cap,
       {
         TimedLaunch tl(ctx, "v2o_clear_balls");
         if (use_seg) {
-          const size_t rows = (size_t)2 * (2 * r + 1) * (2 * r + 1) * sizeof(unsigned long long);
-          const int W = (2 * r + 1 + 63) / 64;
+          const int W = plan.seg_words;
           if (W == 1)
-            clear_balls_seg<1><<<SEG_WGS, 256, rows, st>>>(round_list, counters, live, P1, P2, r, best,
+            clear_balls_seg<1><<<SEG_WGS, 256, plan.seg_rows_bytes, st>>>(round_list, counters, live, P1, P2, r, best,
                                                            C1, C2, S.seg, seg_dilate, seg_force,
                                                            dirty_list, nullptr);
           else if (W == 2)
