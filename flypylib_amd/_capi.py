@@ -623,6 +623,37 @@ class Program:
             precision, _ptr(out), MEM_HOST, odc))
         return out
 
+    def forward_device(self, batch, out=None, precision=PREC_F32):
+        """`forward` device to device: batch (n, D, H, W[, 1]), a contiguous float32 torch
+        tensor on this program's GPU -> (n, d, h, w, c) float32 on the same GPU, written into
+        `out` (a contiguous float32 tensor of that many elements there) when given.  Returns
+        when the context's stream has finished writing it."""
+        import torch
+        x = batch
+        for name, t in (('batch', x),) + ((('out', out),) if out is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError('forward_device: %s must be a contiguous float32 torch tensor' % name)
+            if not t.is_cuda or t.device.index != self.ctx.device:
+                raise TypeError('forward_device: %s must live on this program\'s GPU (cuda:%d), got %s'
+                                % (name, self.ctx.device, t.device))
+        shape = tuple(int(v) for v in x.shape)
+        if len(shape) == 5 and shape[4] == 1:
+            shape = shape[:4]
+        if len(shape) != 4 or min(shape) < 1:
+            raise ValueError('forward_device: batch must be (n, D, H, W[, 1]), got %s' % (tuple(x.shape),))
+        n, in_dims = shape[0], shape[1:]
+        od = self.out_dims(in_dims)
+        if out is None:
+            out = torch.empty((n,) + od, dtype=torch.float32, device=x.device)
+        elif out.numel() != n * int(np.prod(od)):
+            raise ValueError('forward_device: out holds %d values, the output is %s'
+                             % (out.numel(), (n,) + od))
+        odc = (C.c_int32 * 4)()
+        self.ctx.check(self.ctx.lib.fpl_program_forward(
+            self.ctx.h, self.h, _ptr(x), MEM_DEVICE, n, _arr(in_dims, C.c_int32),
+            precision, _ptr(out), MEM_DEVICE, odc))
+        return out.view((n,) + od)
+
     def infer_volume(self, src, tile_in, offset, mean=0.0, std=1.0,
                      precision=PREC_F32, z_range=(0, -1), dst=None, dims=None):
         """src: numpy (Z,Y,X) uint8/float32, or a device tensor/pointer (then

@@ -44,6 +44,11 @@ MERGE_LIBRARIES is a seventh table of that shape, beside POST_LIBRARIES: libfplm
 merge loop of rm_tbar_multi_pred on the neighbour table libfplnear.so leaves on the device
 (solver='device').  BUILT_LIBRARIES is pinned too, so LIBRARIES, the union of all seven, is what
 build() walks now.
+
+VALID_LIBRARIES is an eighth table of that shape, for what runs between the epochs of training:
+libfplval.so reduces a batch of inference-mode predictions and its labels to the loss and metric
+sums of held-out validation (FplNetwork.evaluate, the val_ columns).  LIBRARIES is pinned as
+well, so build() and build_side() walk WALKED_LIBRARIES, the union of all eight.
 """
 import argparse
 import hashlib
@@ -86,6 +91,10 @@ MERGE_LIBRARIES = (
     ('merge', 'merge', 'fplg', 'fplmerge.h', 'libfplmerge.so'),        # rm_tbar_multi_pred's merge loop
 )
 LIBRARIES = BUILT_LIBRARIES + MERGE_LIBRARIES
+VALID_LIBRARIES = (
+    ('valid', 'valid', 'fplv', 'fplval.h', 'libfplval.so'),            # held-out validation's sums
+)
+WALKED_LIBRARIES = LIBRARIES + VALID_LIBRARIES
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -203,16 +212,16 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in LIBRARIES:
+    for row in WALKED_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
     """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
-    SOLVE_LIBRARIES, LABEL_LIBRARIES or MERGE_LIBRARIES: same flags, same SHA-stamped rebuild, a
+    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES or VALID_LIBRARIES: same flags, same SHA-stamped rebuild, a
     version script that exports the row's prefix only"""
-    row = next(r for r in LIBRARIES if r[0] == key)
+    row = next(r for r in WALKED_LIBRARIES if r[0] == key)
     _, sub, prefix, header, lib = row
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])

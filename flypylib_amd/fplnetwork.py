@@ -195,13 +195,34 @@ class FplNetwork:
         self.train_network.compile(**self.compile_args)
 
     def train(self, generator, steps_per_epoch, epochs, log_file,
-              save_filepath):
+              save_filepath, validation_data=None, validation_steps=None):
         """reference :112-122: fit from a batch generator, CSV log, per-epoch
-        checkpoint '<save_filepath>_%03d', then rebuild the inference net"""
+        checkpoint '<save_filepath>_%03d', then rebuild the inference net.
+
+        validation_data / validation_steps (not in the reference; Keras' fit_generator
+        keywords): a held-out (data, labels) batch, or a batch generator of its own with the
+        number of batches to draw from it after every epoch.  The network is evaluated on them
+        in inference mode (see `evaluate`) and the CSV gains a val_<name> column for every
+        column, in CSVLogger's sorted order.  The training generator itself is refused."""
         from . import train
         train.fit_generator(self, generator, steps_per_epoch, epochs, log_file,
-                            save_filepath)
+                            save_filepath, validation_data=validation_data,
+                            validation_steps=validation_steps)
         self._set_infer()
+
+    def evaluate(self, data, steps=None, precision='f32'):
+        """loss and metrics of the network in inference mode (BatchNorm on its moving
+        statistics, no Dropout) on held-out batches: a dict with 'loss' and the metrics of
+        `compile_args`, under the names of the CSV log ('acc', 'masked_accuracy', 'lb0l1err',
+        'lb1l1err').  `data`: a (data, labels) pair - one batch, evaluated once - or a batch
+        generator, then `steps` batches are drawn from it; host arrays or tensors on the
+        network's GPU.  Runs on that GPU (libfplhip.so's fp32 forward, libfplval.so's reduction;
+        `precision` other than 'f32' is refused) and changes nothing in the network."""
+        from . import valid
+        batches, steps = valid.as_batches(data, steps, 'evaluate')
+        ev = valid.evaluator_of(self)
+        m = ev.run(batches, steps, precision)
+        return {k: m[k] for k in ev.cols}
 
     # ---- full-volume inference (reference :136-189) -----------------------------
     def infer(self, image, normalize=None, precision=None, device=None):
@@ -352,6 +373,6 @@ class FplNetwork:
     def __getstate__(self):
         d = dict(self.__dict__)
         for k in ('train_single', 'train_network', 'infer_network', '_parallel',
-                  '_parallel_nets', '_trainer'):
+                  '_parallel_nets', '_trainer', '_evaluator'):
             d[k] = None
         return d

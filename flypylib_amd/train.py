@@ -497,22 +497,51 @@ def _single_trainer(network, graph, loss, opt, opt_args):
     return trainer
 
 
-def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
-                  save_filepath, seed=0):
-    graph = network.train_single
-    args = network.compile_args or {}
+def compile_columns(compile_args):
+    """(loss name, sorted log columns) of a network's compile args"""
+    args = compile_args or {}
     loss = args.get('loss', 'binary_crossentropy')
     loss = getattr(loss, '__name__', loss)
     # Keras names a metric column after the function ('accuracy' -> 'acc')
     metric_names = ['acc' if m in ('accuracy', 'acc') else getattr(m, '__name__', m)
                     for m in args.get('metrics', ['accuracy'])]
-    opt = args.get('optimizer', 'adam')
-    if opt not in _OPTIMIZERS:
-        raise NotImplementedError('optimizer %r' % (opt,))
     cols = sorted(set(metric_names + ['loss']))
     for k in cols:
         if k not in _METRICS:
             raise NotImplementedError('metric %r' % (k,))
+    return loss, cols
+
+
+def log_columns(cols, validate):
+    """(CSV header, keys of a row's values in that order): CSVLogger writes 'epoch', then the log
+    keys sorted - with validation every column and its 'val_' twin"""
+    keys = sorted(list(cols) + ['val_' + k for k in cols]) if validate else list(cols)
+    return ['epoch'] + keys, keys
+
+
+def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
+                  save_filepath, seed=0, validation_data=None, validation_steps=None):
+    """validation_data (not in the reference's `train`; Keras' fit_generator has it): a
+    (data, labels) batch or a batch generator of its own; after every epoch `validation_steps`
+    batches of it (1 for a fixed batch) are evaluated in inference mode on the weights just
+    stored in the graph (valid.Evaluator) and the row gains a val_<name> for every column.
+    Under a process group every rank evaluates its own validation_data and the eight sums are
+    all-reduced before the means are taken."""
+    graph = network.train_single
+    args = network.compile_args or {}
+    loss, cols = compile_columns(args)
+    opt = args.get('optimizer', 'adam')
+    if opt not in _OPTIMIZERS:
+        raise NotImplementedError('optimizer %r' % (opt,))
+    val_batches = None
+    if validation_data is not None:
+        if validation_data is generator:
+            raise ValueError('validation_data is the training generator itself: the prefetch worker '
+                             'owns it; give validation a generator (or a (data, labels) batch) of its own')
+        from . import valid
+        val_batches, validation_steps = valid.as_batches(validation_data, validation_steps,
+                                                         'validation_data')
+    header, keys = log_columns(cols, val_batches is not None)
 
     dist = _dist()
     world = dist.get_world_size() if dist else 1
@@ -546,6 +575,10 @@ def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
         towers.set_weights(graph.get_weights())
     else:
         trainer = _single_trainer(network, graph, loss, opt, _OPTIMIZERS[opt])
+    evaluator = None
+    if val_batches is not None:
+        # in-process towers: the evaluator runs on the first tower's GPU
+        evaluator = valid.evaluator_of(network, towers.devices[0] if towers else trainer.ctx.device)
     network.train_reduce_kind = (towers.reduce_kind if towers else
                                  reducer.kind if reducer else 'none')
 
@@ -554,7 +587,7 @@ def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
         f = open(log_file, 'w', newline='')
         writer = csv.writer(f)
         # CSVLogger: 'epoch' then the log keys in sorted order
-        writer.writerow(['epoch'] + cols)
+        writer.writerow(header)
     step_no = getattr(network, '_train_steps_done', 0)
     history = []
     stage = None
@@ -618,6 +651,20 @@ def fit_generator(network, generator, steps_per_epoch, epochs, log_file,
                     t = t.to(torch.device('cuda', trainer.ctx.device))
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
                 vals = [float(v) / world for v in t.cpu()]
+            if evaluator is not None:
+                sums = evaluator.run_sums(val_batches, validation_steps)
+                if world > 1:
+                    # the sums, not the means: ranks may hold different counts per class
+                    import torch
+                    t = torch.from_numpy(sums)
+                    if dist.get_backend() == 'nccl':
+                        t = t.to(torch.device('cuda', trainer.ctx.device))
+                    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                    sums = t.cpu().numpy()
+                vm = _capi.metrics_from_sums([float(v) for v in sums])
+                log = dict(zip(cols, vals))
+                log.update(('val_' + k, vm[k]) for k in cols)
+                vals = [log[k] for k in keys]
             row = (epoch,) + tuple(vals)
             history.append(row)
             if writer:

@@ -56,6 +56,10 @@
             two legs alternating in one process on one trainer; median, min and max of the
             rounds' ms per step and the per-kernel table of each leg; written to
             profiles/train_vol.json
+  validate  held-out validation (FplNetwork.evaluate, the val_ columns): one pass of 4 batches
+            through valid.Evaluator beside 4 training steps on the same resident batches, in one
+            process, medians of 5, for unet_like2 at 64 x 24^3 and vgg_like at 32 x 64^3; and the
+            two kernels of fplv_loss_sums alone (HIP events); written to profiles/validate.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -135,6 +139,70 @@ def train_vol(ctx, rounds=7, steps=8):
         break
     if out is None:
         raise RuntimeError('train_vol: no batch of 32 / 16 / 8 fits')
+    return out
+
+
+def validate_bench(ctx, torch, batches=4, reps=5):
+    """ms of one validation pass of `batches` batches (valid.Evaluator: inference-mode forward +
+    fplv_loss_sums, one download) beside the ms of as many training steps (step + Adam) on the
+    same resident batches, in one process, medians of `reps`; and fplv_loss_sums alone by HIP
+    events on the case's prediction size"""
+    from flypylib_amd import FplNetwork, _capi, fplmodels, valid
+    out = {'batches': batches, 'reps': reps,
+           'note': 'device-resident batches on both sides; ms per pass / per %d steps' % batches}
+    rng = np.random.default_rng(0)
+    for name, batch, patch in (('unet_like2', 64, 24), ('vgg_like', 32, 64)):
+        net = FplNetwork(getattr(fplmodels, name))
+        ev = valid.evaluator_of(net)
+        od = ev.program.out_dims((patch,) * 3)
+        hi = 2 if name == 'vgg_like' else 3
+        pairs = []
+        for _ in range(batches):
+            x = torch.from_numpy(rng.standard_normal((batch,) + (patch,) * 3 + (1,)).astype(np.float32)).to('cuda:0')
+            y = torch.from_numpy(rng.integers(0, hi, (batch,) + od).astype(np.uint8)).to('cuda:0')
+            pairs.append((x, y))
+        loss = getattr(net.compile_args['loss'], '__name__', net.compile_args['loss']) \
+            if net.compile_args else 'binary_crossentropy'
+        tr = _capi.Trainer(ctx, net.train_single, loss=loss)
+
+        def val_pass():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev.run_sums(iter(pairs), batches)
+            return (time.perf_counter() - t0) * 1e3
+
+        def train_steps():
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for s, (x, y) in enumerate(pairs):
+                tr.step(x, y, seed=s); tr.apply(1.0)
+            tr.metrics()
+            ctx.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        val_pass(); train_steps()                      # warm-up: both sides' buffers exist
+        v = [val_pass() for _ in range(reps)]
+        t = [train_steps() for _ in range(reps)]
+        n = batch * int(np.prod(od))
+        pred, lab = torch.rand(n, device='cuda:0'), pairs[0][1].reshape(-1)
+        sums = torch.zeros(8, dtype=torch.float64, device='cuda:0')
+        kern = []
+        for _ in range(reps + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            valid.loss_sums_device(pred, lab, loss, sums=sums, scratch=ev.scratch)
+            b.record(); b.synchronize()
+            kern.append(a.elapsed_time(b))
+        tr.close()
+        vm, tm = float(np.median(v)), float(np.median(t))
+        out['%s_%dx%d' % (name, batch, patch)] = {
+            'loss': loss, 'elements_per_batch': n,
+            'validation_pass_ms': round(vm, 3), 'validation_ms_per_batch': round(vm / batches, 3),
+            'validation_runs_ms': [round(x, 3) for x in v],
+            'training_steps_ms': round(tm, 3), 'training_ms_per_step': round(tm / batches, 3),
+            'training_runs_ms': [round(x, 3) for x in t],
+            'validation_over_training': round(vm / tm, 4),
+            'loss_sums_kernels_ms': round(float(np.median(kern[1:])), 4)}
+        print(json.dumps(out['%s_%dx%d' % (name, batch, patch)]), flush=True)
     return out
 
 
@@ -954,6 +1022,11 @@ def main():
         print(json.dumps(res['train_vol']), flush=True)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'train_vol.json')
+
+    if 'validate' in what:
+        res['validate'] = validate_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'validate.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
