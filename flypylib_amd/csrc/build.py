@@ -49,6 +49,11 @@ VALID_LIBRARIES is an eighth table of that shape, for what runs between the epoc
 libfplval.so reduces a batch of inference-mode predictions and its labels to the loss and metric
 sums of held-out validation (FplNetwork.evaluate, the val_ columns).  LIBRARIES is pinned as
 well, so build() and build_side() walk WALKED_LIBRARIES, the union of all eight.
+
+PREP_LIBRARIES is a ninth table of that shape, for what runs before any network sees a volume:
+libfplclahe.so is the per-slice contrast-limited adaptive histogram equalisation of
+fplutils.clahe(device=...).  WALKED_LIBRARIES is pinned too, so build() and build_side() walk
+PREPARED_LIBRARIES, the union of all nine; its binding loads lazily, when a call asks for a device.
 """
 import argparse
 import hashlib
@@ -95,6 +100,10 @@ VALID_LIBRARIES = (
     ('valid', 'valid', 'fplv', 'fplval.h', 'libfplval.so'),            # held-out validation's sums
 )
 WALKED_LIBRARIES = LIBRARIES + VALID_LIBRARIES
+PREP_LIBRARIES = (
+    ('clahe', 'clahe', 'fplc', 'fplclahe.h', 'libfplclahe.so'),        # fplutils.clahe
+)
+PREPARED_LIBRARIES = WALKED_LIBRARIES + PREP_LIBRARIES
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -212,16 +221,17 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in WALKED_LIBRARIES:
+    for row in PREPARED_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
     """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
-    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES or VALID_LIBRARIES: same flags, same SHA-stamped rebuild, a
+    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES, VALID_LIBRARIES or PREP_LIBRARIES: same flags,
+    same SHA-stamped rebuild, a
     version script that exports the row's prefix only"""
-    row = next(r for r in WALKED_LIBRARIES if r[0] == key)
+    row = next(r for r in PREPARED_LIBRARIES if r[0] == key)
     _, sub, prefix, header, lib = row
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])

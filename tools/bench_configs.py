@@ -60,6 +60,11 @@
             through valid.Evaluator beside 4 training steps on the same resident batches, in one
             process, medians of 5, for unet_like2 at 64 x 24^3 and vgg_like at 32 x 64^3; and the
             two kernels of fplv_loss_sums alone (HIP events); written to profiles/validate.json
+  clahe     fplutils.clahe at --clahe-size^3 (default 520; the synthetic uint8 volume of synth.py),
+            kernel_size 64, all in one process, one warm-up and then the median, min and max of 5:
+            the numpy specification on the host (single-threaded by construction, whatever the
+            cores), clahe(device=0) from a host array, clahe(device=0) from a resident tensor, and
+            the four stages of fplc_clahe alone (HIP events); written to profiles/clahe.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -805,10 +810,65 @@ def labels_bench(ctx, torch, sizes=(520, 256), reps=5):
     return rows
 
 
+def clahe_bench(ctx, torch, n=520, k=64, reps=5):
+    """fplutils.clahe: the numpy specification against device=, in one process"""
+    from flypylib_amd import _clahecapi, clahe, fplutils, synth
+    dev = torch.device('cuda', ctx.device)
+    im = synth.em_volume_u8(3, (n, n, n))
+    row = dict(volume=[n, n, n], voxels=n ** 3, dtype='uint8', kernel_size=k, clip_limit=0.01, nbins=256,
+               reps=reps, timing='one warm-up, then median / min / max of %d, ms' % reps,
+               host_note='clahe_numpy is single-threaded by construction; the cores of the machine '
+                         'do not enter')
+
+    def stats(ts):
+        return dict(median=float(np.median(ts)), min=float(min(ts)), max=float(max(ts)))
+
+    def timed(fn, sync):
+        ts, r = [], None
+        for i in range(reps + 1):
+            t0 = time.perf_counter()
+            r = fn()
+            if sync:
+                torch.cuda.synchronize(dev)
+            if i:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        return stats(ts), r
+
+    row['host_ms'], host = timed(lambda: fplutils.clahe(im, k), False)
+    row['device_from_host_ms'], got = timed(lambda: fplutils.clahe(im, k, device=ctx.device), True)
+    res = torch.from_numpy(im).to(dev)
+    row['device_resident_ms'], got_r = timed(lambda: fplutils.clahe(res, k, device=ctx.device), True)
+    row['identical'] = bool(np.array_equal(got.cpu().numpy(), host) and torch.equal(got, got_r))
+    row['host_over_device_resident'] = row['host_ms']['median'] / row['device_resident_ms']['median']
+    del host, got_r
+    need = _clahecapi.scratch_bytes(n, n, n, k, k, 256)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    row['scratch_bytes'] = int(need)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    stages = (('range', _clahecapi.STAGE_RANGE), ('maps', _clahecapi.STAGE_MAPS),
+              ('apply', _clahecapi.STAGE_APPLY), ('finish', _clahecapi.STAGE_FINISH))
+    ms = {name: [] for name, _ in stages}
+    for i in range(reps + 1):
+        for name, stage in stages:
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            _clahecapi.clahe(res, True, (n, n, n), (k, k), clahe.clip_count(0.01, k, k), 256, False, got,
+                             scratch, need, stage, stream)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+    row['kernels_ms'] = {name: stats(v) for name, v in ms.items()}
+    row['kernels_timing'] = 'HIP events around one stage of fplc_clahe on the resident volume'
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
     ap.add_argument('--what', default='unet,train,v2o,pipeline')
+    ap.add_argument('--clahe-size', type=int, default=520)
     ap.add_argument('--unet-size', type=int, default=264)
     ap.add_argument('--roi-precision', default='auto')
     ap.add_argument('--vgg2-size', type=int, default=1024)
@@ -1027,6 +1087,11 @@ def main():
         res['validate'] = validate_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'validate.json')
+
+    if 'clahe' in what:
+        res['clahe'] = clahe_bench(ctx, torch, a.clahe_size)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'clahe.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
