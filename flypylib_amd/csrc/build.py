@@ -54,6 +54,13 @@ PREP_LIBRARIES is a ninth table of that shape, for what runs before any network 
 libfplclahe.so is the per-slice contrast-limited adaptive histogram equalisation of
 fplutils.clahe(device=...).  WALKED_LIBRARIES is pinned too, so build() and build_side() walk
 PREPARED_LIBRARIES, the union of all nine; its binding loads lazily, when a call asks for a device.
+
+ROI_LIBRARIES is a tenth table of that shape, for the first stage of the workflow, the export of
+training substacks: libfplroi.so renders a BlockRoi's mask of a box, answers point queries and
+voxel counts from the ROI's runs, and cuts and normalises a training cube
+(roi.BlockRoi(device=...), fplsynapses.roi_to_substacks(device=...)).  PREPARED_LIBRARIES is pinned
+as well, so build() and build_side() walk EXPORT_LIBRARIES, the union of all ten; its binding loads
+lazily too.
 """
 import argparse
 import hashlib
@@ -104,6 +111,10 @@ PREP_LIBRARIES = (
     ('clahe', 'clahe', 'fplc', 'fplclahe.h', 'libfplclahe.so'),        # fplutils.clahe
 )
 PREPARED_LIBRARIES = WALKED_LIBRARIES + PREP_LIBRARIES
+ROI_LIBRARIES = (
+    ('roi', 'roi', 'fplr', 'fplroi.h', 'libfplroi.so'),                # BlockRoi, roi_to_substacks
+)
+EXPORT_LIBRARIES = PREPARED_LIBRARIES + ROI_LIBRARIES
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -221,17 +232,16 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in PREPARED_LIBRARIES:
+    for row in EXPORT_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
     """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
-    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES, VALID_LIBRARIES or PREP_LIBRARIES: same flags,
-    same SHA-stamped rebuild, a
-    version script that exports the row's prefix only"""
-    row = next(r for r in PREPARED_LIBRARIES if r[0] == key)
+    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES, VALID_LIBRARIES, PREP_LIBRARIES or
+    ROI_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the row's prefix only"""
+    row = next(r for r in EXPORT_LIBRARIES if r[0] == key)
     _, sub, prefix, header, lib = row
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])

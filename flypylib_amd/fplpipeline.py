@@ -357,7 +357,7 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
                        instance_name='grayscale',
                        dvid_seg_info=None, precision=None, timings=None,
                        neighbor_thresh=None, merge_method='sparse', merge_device=None,
-                       merge_solver='host'):
+                       merge_solver='host', roi=None):
     """Predictions of a trained network within the substacks of an ROI, cached per
     substack in `working_dir` (reference :841-986; same arguments).  `dvid_roi` is
     an ROI text file (`roi_from_txt`) or a list of `szyx`; `precision` overrides the
@@ -369,7 +369,12 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
     (fplsynapses.rm_tbar_multi_pred with method=`merge_method`, device=`merge_device`,
     solver=`merge_solver` - 'device' runs the merge loop on the GPU too - and merge_multi_pred), writes the merged list to `all_merged.p` beside it and returns it; the
     other ranks return the unmerged list.  With a segmentation (`dvid_seg_info`) the points'
-    labels are read from it at the rounded locations, else all labels are equal."""
+    labels are read from it at the rounded locations, else all labels are equal.
+
+    roi=None (default): nothing more.  With a `roi.BlockRoi`, the concatenated point list is
+    filtered as the reference filters it with DVID's roi_ptquery (:974-980) - the points whose
+    np.fliplr(locs).astype('int') lie in the ROI are kept - before `all.p` is written, and so
+    before the merge.  The filter is the host `ptquery`: the list is small."""
     # the reference reads a 'segmentation' labelmap from a second DVID node
     # (dvid_seg_info = [server, uuid]); here it is a label volume with the image's
     # extents: array-like, 'npy://file', or a volume already resident on the GPU
@@ -380,6 +385,7 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
         os.makedirs(d, exist_ok=True)
     norm_dir = '%s/norm' % working_dir
     src = _open_source(data_source)
+    block_roi = roi                   # `roi` below is the reference's name for the substack list
     roi = roi_from_txt(dvid_roi) if isinstance(dvid_roi, str) else [[szyx(*r) for r in dvid_roi]]
     rank, world, dist = _rank_world()
 
@@ -601,6 +607,8 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
         conf.append(obj['conf'])
     obj = {'locs': np.concatenate(locs) if locs else np.zeros((0, 3)),
            'conf': np.concatenate(conf) if conf else np.zeros(0)}
+    if block_roi is not None:
+        obj = filter_by_roi(obj, block_roi)
     if missing:
         import warnings
         warnings.warn('full_roi_inference: %d of %d substacks belong to other ranks and there '
@@ -616,6 +624,16 @@ def full_roi_inference(data_source, dvid_uuid, dvid_roi,
             with open('%s/all_merged.p' % working_dir, 'wb') as f_out:
                 pickle.dump(obj, f_out)
     return obj
+
+
+def filter_by_roi(tbars, roi):
+    """the points of a {'locs' (x, y, z), 'conf'} list inside the `roi.BlockRoi`, asked as the
+    reference asks DVID (fplobjdetect.py:974-980): at np.fliplr(locs).astype('int')"""
+    locs, conf = np.asarray(tbars['locs']), np.asarray(tbars['conf'])
+    if conf.size == 0:
+        return {'locs': locs, 'conf': conf}
+    in_roi = roi.ptquery(np.fliplr(locs).astype('int'))
+    return {'locs': locs[in_roi], 'conf': conf[in_roi]}
 
 
 def merge_border_duplicates(tbars, neighbor_thresh, seg_src=None, method='sparse', device=None,

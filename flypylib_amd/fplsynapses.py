@@ -1,9 +1,10 @@
 """Synapse (T-bar) point lists as JSON - the data formats on the output side of the
 detection path (reference `flypylib/fplsynapses.py:11-111`) - and the label / mask
 volumes training is fed from (`write_labels_mask`, :251-310), and the merging of duplicate
-detections along substack borders (`rm_tbar_multi_pred`, :378-449).  The DVID push / ROI /
-annotation-editing helpers of the reference need `libdvid` and are not part of this
-package."""
+detections along substack borders (`rm_tbar_multi_pred`, :378-449), and the export of training
+substacks (`roi_to_substacks`, `get_substack_annotations`, :140-249) on arrays and a
+`roi.BlockRoi` in place of a DVID node.  The DVID push and annotation-editing helpers of the
+reference need `libdvid` and are not part of this package."""
 import json
 import os
 
@@ -381,3 +382,208 @@ def merge_multi_pred(tbars, rm_idx, mv_idx, mv_loc):
     locs[mv_idx] = np.asarray(mv_loc)[mv_idx]
     keep = np.logical_not(rm_idx)
     return {'locs': locs[keep], 'conf': np.asarray(tbars['conf'])[keep]}
+
+
+# ---- training-data export (reference :140-249), on arrays ---------------------------------------------
+
+def _annotations(dvid_annotations):
+    """{'locs' (N, 3) global (x, y, z), 'conf' (N,)} of a point dict or of anything
+    load_from_json reads"""
+    tt = dvid_annotations if isinstance(dvid_annotations, dict) else load_from_json(dvid_annotations)
+    locs, conf = np.asarray(tt['locs']), np.asarray(tt['conf'])
+    return {'locs': locs.reshape(-1, 3) if locs.size == 0 else locs, 'conf': conf.reshape(-1)}
+
+
+def get_substack_annotations(annotations, roi, ss, device=None):
+    """the annotations inside the substack `ss` and inside the ROI (reference :236-249).
+    `annotations`: a {'locs', 'conf'} dict in global (x, y, z), or anything load_from_json reads.
+    Kept are the points with ss.x <= x < ss.x + ss.size, and likewise for y and z - the box
+    DVID's elements/<size>/<offset> answers - and of those the points `roi.ptquery` accepts at
+    np.fliplr(locs).astype('int'), as the reference asks roi_ptquery; roi=None filters by the
+    box alone.  `device` is roi.ptquery's.  -> a new {'locs', 'conf'}"""
+    tt = _annotations(annotations)
+    locs, conf = tt['locs'], tt['conf']
+    lo = np.asarray([ss.x, ss.y, ss.z])
+    keep = np.all((locs >= lo) & (locs < lo + ss.size), axis=1) if len(locs) else np.zeros(0, bool)
+    locs, conf = locs[keep], conf[keep]
+    if roi is not None and conf.size > 0:
+        in_roi = roi.ptquery(np.fliplr(locs).astype('int'), device=device)
+        locs, conf = locs[in_roi], conf[in_roi]
+    return {'locs': locs, 'conf': conf}
+
+
+def _substacks_of(dvid_roi, partition_size, roi):
+    """(substacks, BlockRoi) of roi_to_substacks' `dvid_roi` and `roi=`"""
+    from . import fplpipeline
+    from .roi import BlockRoi
+    if isinstance(dvid_roi, str) and os.path.isfile(dvid_roi):
+        with open(dvid_roi) as f_in:
+            is_json = f_in.read(64).lstrip().startswith('[')
+        if not is_json:
+            if not isinstance(roi, BlockRoi):
+                raise ValueError('dvid_roi %r lists substacks and holds no ROI to mask or filter by: '
+                                 'pass the BlockRoi as roi=' % (dvid_roi,))
+            print('reading roi %s from file' % dvid_roi)
+            return fplpipeline.roi_from_txt(dvid_roi)[0], roi
+        dvid_roi = BlockRoi.from_json(dvid_roi)
+    if not isinstance(dvid_roi, BlockRoi):
+        raise ValueError('dvid_roi is a BlockRoi, the path of its JSON or a substack text file, got %r'
+                         % (dvid_roi,))
+    if roi is not None:
+        raise ValueError('roi= goes with a substack text file; dvid_roi is an ROI already')
+    return dvid_roi.partition(partition_size)[0], dvid_roi
+
+
+def _write_volume(base, arr):
+    from . import keras_io
+    keras_io.write_main(base + '.h5', arr)
+    np.save(base + '.npy', arr)
+
+
+def roi_to_substacks(dvid_server, dvid_uuid, dvid_roi, dvid_annotations, partition_size,
+                     data_dir=None, substack_ids=None, image_normalize=None, buffer_size=None,
+                     radius_use=None, radius_ign=None, seg_name=None, device=None, roi=None):
+    """Training substacks of an ROI (reference :140-233), on arrays instead of a DVID node.  The
+    parameter order is the reference's; the parameters mean:
+
+      dvid_server       the grayscale: whatever fplpipeline's sources accept - a uint8 (Z, Y, X)
+                        array or memmap, 'npy://file', a resident uint8 tensor / DeviceBuffer
+      dvid_uuid         ignored
+      dvid_roi          a roi.BlockRoi or the path of its JSON: the substacks are its
+                        partition(partition_size); or a substack text file (roi_from_txt): the
+                        substacks are the file's, and the ROI to mask and filter by comes as
+                        `roi=` (without it: ValueError)
+      dvid_annotations  a {'locs', 'conf'} dict in global (x, y, z), or anything load_from_json reads
+      seg_name          a label volume with the image's extents (array, 'npy://file', resident), or None
+
+    substack_ids=None prints the reference's statistics, '%03d\\t%.03f\\t%3d' of index, fraction of
+    the cube inside the ROI (from BlockRoi.voxel_counts: nothing is rendered) and annotations in
+    cube and ROI, and returns the rows [(index, fraction, count)] (the reference returns None).
+
+    Otherwise, for each id: the cube with `buffer_size` voxels around it, zeros outside the
+    volume, as float32 (v - image_normalize[0]) / image_normalize[1] with both rounded to
+    float32; the annotations in the cube's local coordinates; the ROI mask; write_labels_mask;
+    the segmentation cube (uint64) if asked for.  With `data_dir` they are written under the
+    reference's names - '%03d_im%g_%g_bf%d', '%03d_bf%d_synapses.json', '%03d_bf%d_roimask',
+    '%03d_ru%d_ri%d_bf%d_{labels,mask}', '%03d_seg_bf%d' - each volume as '.h5' (dataset 'main',
+    uncompressed: the reference gzips) and as '.npy' beside it.  -> a list of dicts, one per id:
+    id, substack, image, tbars, roi_mask, labels, mask, seg (None without seg_name).
+
+    device=None is numpy throughout.  device=<int> (or True) uploads the grayscale once (or
+    takes it resident), cuts and normalises with libfplroi.so, renders the mask there, filters
+    the annotations there, calls write_labels_mask(device=) on the resident mask and cuts a
+    resident segmentation through libfplseg.so (int64 tensor holding the uint64 bits; a host
+    segmentation is cut on the host): image, roi_mask, labels and mask are resident torch
+    tensors, equal to the host's arrays bit for bit, and each file is written from one download.
+    No host fallback: a missing library raises."""
+    from . import fplpipeline
+    subs, roi = _substacks_of(dvid_roi, partition_size, roi)
+    tbars_all = _annotations(dvid_annotations)
+    if substack_ids is None:
+        boxes = np.asarray([(ss.z, ss.y, ss.x, ss.size, ss.size, ss.size) for ss in subs],
+                           np.int64).reshape(-1, 6)
+        counts = roi.voxel_counts(boxes, device=device)
+        rows = []
+        for ii, ss in enumerate(subs):
+            frac_in = int(counts[ii]) / float(ss.size ** 3)
+            tt = get_substack_annotations(tbars_all, roi, ss, device=device)
+            print('%03d\t%.03f\t%3d' % (ii, frac_in, tt['conf'].size))
+            rows.append((ii, frac_in, int(tt['conf'].size)))
+        return rows
+
+    if not hasattr(substack_ids, '__len__'):
+        substack_ids = [substack_ids, ]
+    src = fplpipeline._open_source(dvid_server)
+    seg_src = None if seg_name is None else fplpipeline._open_label_source(seg_name)
+    mean, std = np.float32(image_normalize[0]), np.float32(image_normalize[1])
+    dev = gray = None
+    if device is not None:
+        from . import roi as _roi
+        dev = _roi.torch_device(device)
+        gray = _resident_gray(src, dev)
+    out = []
+    for ii in substack_ids:
+        print(ii)
+        ss = subs[ii]
+        image_sz = ss.size + 2 * buffer_size
+        image_offset = [ss.z - buffer_size, ss.y - buffer_size, ss.x - buffer_size]
+        dims = [image_sz] * 3
+
+        # the image with its buffer
+        if dev is None or gray is None:
+            cube = src.cube_host(image_offset, image_sz)
+            if cube is None:
+                cube = np.zeros(dims, np.uint8)
+        if dev is None:
+            image = (cube.astype('float32') - mean) / std
+        elif gray is None:                    # a generated source: the cube goes up, not the volume
+            import torch
+            image = _roi.cut_normalize_device(torch.from_numpy(cube).to(dev), dims, (0, 0, 0), dims,
+                                              mean, std, dev)
+        else:
+            image = _roi.cut_normalize_device(gray, src.extent, image_offset, dims, mean, std, dev)
+
+        # the annotations, in local coordinates
+        tt = get_substack_annotations(tbars_all, roi, ss, device=device)
+        if tt['conf'].size > 0:
+            tt['locs'] = tt['locs'] - np.fliplr(np.asarray([image_offset]))
+
+        # labels and mask, with the ROI and the buffer
+        mask = roi.roi3D(dims, image_offset, device=device)
+        prefix = None
+        if data_dir is not None:
+            _write_volume('%s/%03d_im%g_%g_bf%d' % (data_dir, ii, image_normalize[0],
+                                                    image_normalize[1], buffer_size),
+                          image if dev is None else image.cpu().numpy())
+            tbars_to_json_format_raveler(tt, '%s/%03d_bf%d_synapses.json' % (data_dir, ii, buffer_size))
+            _write_volume('%s/%03d_bf%d_roimask' % (data_dir, ii, buffer_size),
+                          mask if dev is None else mask.cpu().numpy())
+            prefix = '%s/%03d_ru%d_ri%d_bf%d' % (data_dir, ii, radius_use, radius_ign, buffer_size)
+        labels, lmask = write_labels_mask(tt, mask, radius_use, radius_ign, buffer_size, prefix,
+                                          device=device)
+
+        # the segmentation
+        seg = None
+        if seg_src is not None:
+            seg = _seg_cube(seg_src, image_offset, image_sz, dev)
+            if data_dir is not None:
+                _write_volume('%s/%03d_seg_bf%d' % (data_dir, ii, buffer_size),
+                              seg if isinstance(seg, np.ndarray) else seg.cpu().numpy().view(np.uint64))
+        out.append({'id': ii, 'substack': ss, 'image': image, 'tbars': tt, 'roi_mask': mask,
+                    'labels': labels, 'mask': lmask, 'seg': seg})
+    return out
+
+
+def _resident_gray(src, dev):
+    """the grayscale of `src` on `dev`: a resident source as it is, a host uint8 array uploaded
+    once, None for a source that generates its cubes"""
+    from . import fplpipeline
+    import torch
+    if isinstance(src, fplpipeline._DeviceSource):
+        if src.device != (dev.index or 0):
+            raise ValueError('the grayscale lives on GPU %d, device= names %s' % (src.device, dev))
+        return src.vol
+    if isinstance(src, fplpipeline._ArraySource):
+        if np.dtype(src.arr.dtype) != np.uint8:
+            raise ValueError('roi_to_substacks(device=) takes uint8 grayscale, not %s' % src.arr.dtype)
+        return torch.from_numpy(np.array(src.arr, np.uint8, order='C')).to(dev)
+    return None
+
+
+def _seg_cube(seg_src, origin, size, dev):
+    """the uint64 (size,)*3 cube of the label source at `origin`, zeros outside the volume: a host
+    source on the host; a resident one through libfplseg.so, as an int64 tensor of the same bits"""
+    from . import fplpipeline
+    if isinstance(seg_src, fplpipeline._DeviceLabelSource):
+        from . import _segcapi
+        import torch
+        where = torch.device('cuda', seg_src.device)
+        if dev is not None and where != dev:
+            raise ValueError('the segmentation lives on %s, device= names %s' % (where, dev))
+        dst = torch.empty((size,) * 3, dtype=torch.int64, device=where)
+        with torch.cuda.device(where):
+            _segcapi.pad_box(seg_src.vol, origin, (size,) * 3, 0, dst,
+                             torch.cuda.current_stream(where).cuda_stream)
+        return dst
+    cube = seg_src.cube_host(origin, size, np.uint64)
+    return np.zeros((size,) * 3, np.uint64) if cube is None else cube

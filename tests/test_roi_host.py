@@ -1,0 +1,443 @@
+"""roi.BlockRoi, the numpy specification of the ROI services, the host roi_to_substacks /
+get_substack_annotations against the reference's own run (tests/golden/roi_to_substacks.npz),
+full_roi_inference(roi=), and the build row and C ABI of libfplroi.so."""
+import hashlib
+import json
+import os
+import pickle
+import re
+
+import numpy as np
+import pytest
+
+from flypylib_amd import _roicapi, _sidelib, fplobjdetect, fplpipeline, fplsynapses, fplutils, keras_io
+from flypylib_amd.csrc import build
+from flypylib_amd.roi import BlockRoi
+from tests import side_abi_cases as abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'roi_to_substacks.npz')
+N_EXPORTS = 6
+
+
+def irregular_roi(block_size, seed=3, shape=(5, 6, 7), origin=(-2, 1, -3)):
+    rs = np.random.RandomState(seed)
+    mask = rs.rand(*shape) < 0.45
+    mask[2, 3, :] = False                          # a missing block row between present ones
+    mask[1, 1, :] = [1, 0, 1, 1, 0, 0, 1]          # two runs one block apart
+    return BlockRoi.from_block_mask(mask, origin, block_size), mask, origin
+
+
+def brute_roi3d(mask, origin, b, dims, offset):
+    """np.repeat of the dense block mask, embedded in a frame that holds the box"""
+    lo = [min(o * b, off) for o, off in zip(origin, offset)]
+    hi = [max((o + n) * b, off + d) for o, n, off, d in zip(origin, mask.shape, offset, dims)]
+    frame = np.zeros([h - l for l, h in zip(lo, hi)], np.uint8)
+    dense = np.repeat(np.repeat(np.repeat(mask, b, 0), b, 1), b, 2).astype(np.uint8)
+    at = [o * b - l for o, l in zip(origin, lo)]
+    frame[at[0]:at[0] + dense.shape[0], at[1]:at[1] + dense.shape[1], at[2]:at[2] + dense.shape[2]] = dense
+    s = [off - l for off, l in zip(offset, lo)]
+    return frame[s[0]:s[0] + dims[0], s[1]:s[1] + dims[1], s[2]:s[2] + dims[2]]
+
+
+def boxes_for(b, mask, origin):
+    oz, oy, ox = (o * b for o in origin)
+    ez, ey, ex = ((o + n) * b for o, n in zip(origin, mask.shape))
+    return [((2 * b, 3 * b, 2 * b), (oz, oy, ox)),                        # aligned
+            ((2 * b + 1, b + 3, 3 * b - 1), (oz + 1, oy + b - 1, ox + 2)),  # unaligned
+            ((3 * b, 2 * b, 2 * b + 3), (oz - b - 1, oy - 2, ox - b - 3)),  # from negative coordinates
+            ((5, 4, 6), (ez + 3 * b, ey, ex + b)),                        # wholly outside
+            ((1, 1, 1), (oz + b, oy + b, ox)),                            # one voxel
+            (tuple(n * b + 2 for n in mask.shape), (oz - 1, oy - 1, ox - 1))]  # all of it
+
+
+# ---- the object -------------------------------------------------------------------------------------
+
+def test_canonicalisation_merges_sorts_and_refuses():
+    roi = BlockRoi([[1, 0, 5, 6], [0, 2, 3, 4], [1, 0, 0, 2], [1, 0, 3, 3], [0, 2, 4, 8], [1, 0, 8, 9],
+                    [-1, 0, 0, 0]], 4)
+    assert roi.runs.tolist() == [[-1, 0, 0, 0], [0, 2, 3, 8], [1, 0, 0, 3], [1, 0, 5, 6], [1, 0, 8, 9]]
+    assert roi.n_blocks == 1 + 6 + 4 + 2 + 2 and roi.block_size == 4 and len(roi) == 5
+    assert roi == BlockRoi(roi.runs[::-1], 4) and roi != BlockRoi(roi.runs, 8)
+    assert roi.row_keys.tolist() == sorted(roi.row_keys.tolist()) and len(roi.row_keys) == 3
+    assert roi.row_start.tolist() == [0, 1, 2, 5] and roi.runs_x.dtype == np.int32
+    with pytest.raises(ValueError, match='x1 2 < x0 3'):
+        BlockRoi([[0, 0, 3, 2]])
+    for bad in (np.zeros((2, 3), int), np.zeros((2, 4, 1), int), np.zeros(4, int)):
+        with pytest.raises(ValueError, match=r'\(n, 4\)'):
+            BlockRoi(bad)
+    with pytest.raises(ValueError, match='integers'):
+        BlockRoi(np.zeros((1, 4)))
+    empty = BlockRoi(np.zeros((0, 4), int))
+    assert len(empty) == 0 and empty.n_blocks == 0 and BlockRoi([]).runs.shape == (0, 4)
+    assert empty.block_mask()[0].shape == (0, 0, 0) and empty.partition(2) == ([], 0.0)
+    assert 'floor division' in BlockRoi.__doc__ and 'DVID cannot be consulted' in BlockRoi.__doc__
+
+
+def test_json_and_block_mask_round_trips(tmp_path):
+    roi, mask, origin = irregular_roi(4)
+    text = roi.to_json()
+    assert json.loads(text) == roi.runs.tolist()
+    assert BlockRoi.from_json(text, 4) == roi
+    path = str(tmp_path / 'roi.json')
+    assert roi.to_json(path) == text and BlockRoi.from_json(path, 4) == roi
+    assert BlockRoi.from_json('[]').runs.shape == (0, 4) and BlockRoi.from_json('null').n_blocks == 0
+    got, at = roi.block_mask()
+    full = np.zeros(mask.shape, bool)
+    lo = [a - o for a, o in zip(at, origin)]
+    full[lo[0]:lo[0] + got.shape[0], lo[1]:lo[1] + got.shape[1], lo[2]:lo[2] + got.shape[2]] = got
+    assert np.array_equal(full, mask) and roi.n_blocks == mask.sum()
+    assert BlockRoi.from_block_mask(got, at, 4) == roi
+
+
+@pytest.mark.parametrize('b', [32, 4])
+def test_roi3d_is_the_repeated_block_mask(b):
+    roi, mask, origin = irregular_roi(b)
+    empty = BlockRoi([], b)
+    for dims, offset in boxes_for(b, mask, origin):
+        got = roi.roi3D(dims, offset)
+        assert got.dtype == np.uint8 and got.shape == tuple(dims)
+        assert np.array_equal(got, brute_roi3d(mask, origin, b, dims, offset)), (dims, offset)
+        assert not empty.roi3D(dims, offset).any()
+    assert roi.roi3D((0, 3, 3), (0, 0, 0)).shape == (0, 3, 3)
+
+
+@pytest.mark.parametrize('b', [32, 4])
+def test_ptquery_is_a_roi3d_lookup(b):
+    roi, mask, origin = irregular_roi(b)
+    lo = np.asarray([o * b - b for o in origin])
+    dims = [(n + 2) * b for n in mask.shape]
+    dense = roi.roi3D(dims, lo)
+    rs = np.random.RandomState(b)
+    pts = lo + rs.randint(0, min(dims), (400, 3)) % np.asarray(dims)
+    edge = []
+    for z, y, x0, x1 in roi.runs.tolist():          # the voxels x0 b, x1 b + b - 1 and x1 b + b
+        for x in (x0 * b - 1, x0 * b, x1 * b + b - 1, x1 * b + b):
+            edge.append((z * b, y * b + b - 1, x))
+    pts = np.concatenate([pts, np.asarray(edge)])
+    got = roi.ptquery(pts)
+    at = pts - lo
+    assert got.dtype == bool and np.array_equal(got, dense[at[:, 0], at[:, 1], at[:, 2]] != 0)
+    assert got[400:].reshape(-1, 4).tolist() == [[False, True, True, False]] * len(roi.runs)
+    far = np.asarray([[2 ** 45, 0, 0], [-2 ** 45, -1, -1]])
+    assert not roi.ptquery(far).any() and roi.ptquery(np.zeros((0, 3), int)).shape == (0,)
+    assert not BlockRoi([], b).ptquery(pts).any()
+    with pytest.raises(ValueError, match='integer'):
+        roi.ptquery(np.zeros((2, 3)))
+
+
+@pytest.mark.parametrize('b', [32, 4])
+def test_voxel_counts_is_the_sum_of_roi3d(b):
+    roi, mask, origin = irregular_roi(b)
+    boxes = np.asarray([tuple(off) + tuple(d) for d, off in boxes_for(b, mask, origin)], np.int64)
+    want = [int(roi.roi3D(bx[3:], bx[:3]).sum()) for bx in boxes]
+    got = roi.voxel_counts(boxes)
+    assert got.dtype == np.int64 and got.tolist() == want and want[-1] == mask.sum() * b ** 3
+    assert roi.voxel_counts(np.zeros((0, 6), np.int64)).shape == (0,)
+    assert BlockRoi([], b).voxel_counts(boxes).tolist() == [0] * len(boxes)
+    solid = BlockRoi([[z, y, 0, 63] for z in range(64) for y in range(64)], 32)
+    assert solid.voxel_counts([[0, 0, 0, 2048, 2048, 2048]]).tolist() == [2 ** 33]
+
+
+@pytest.mark.parametrize('p', [1, 2, 3])
+def test_partition_covers_every_block_once(p):
+    roi, mask, origin = irregular_roi(4)
+    subs, packing = roi.partition(p)
+    side = 4 * p
+    assert all(isinstance(s, fplutils.szyx) and s.size == side for s in subs)
+    corners = [(s.z, s.y, s.x) for s in subs]
+    assert corners == sorted(corners) and len(set(corners)) == len(corners)
+    assert all(c % side == 0 for corner in corners for c in corner)
+    counts = roi.voxel_counts([(s.z, s.y, s.x, side, side, side) for s in subs])
+    assert counts.min() >= 4 ** 3 and counts.sum() == roi.n_blocks * 4 ** 3     # none empty, each block once
+    assert packing == roi.n_blocks / float(len(subs) * p ** 3)
+    if p == 1:
+        assert len(subs) == roi.n_blocks and packing == 1.0
+    with pytest.raises(ValueError, match='partition_size'):
+        roi.partition(0)
+    assert 'unpinned against DVID' in BlockRoi.partition.__doc__
+
+
+# ---- roi_to_substacks against the reference's own run ---------------------------------------------
+
+def _sha(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(('%s%r' % (a.dtype.str, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+@pytest.fixture(scope='module')
+def golden():
+    g = dict(np.load(GOLDEN))
+    g['roi'] = BlockRoi(g['runs'], int(g['block_size']))
+    g['tbars'] = {'locs': g['locs'], 'conf': g['conf']}
+    g['kw'] = dict(image_normalize=g['image_normalize'].tolist(), buffer_size=int(g['buffer_size']),
+                   radius_use=int(g['radius_use']), radius_ign=int(g['radius_ign']))
+    return g
+
+
+def export(g, data_dir, device=None, **over):
+    kw = dict(g['kw'], data_dir=data_dir, substack_ids=g['ids'].tolist(), seg_name=g['seg'], device=device)
+    kw.update(over)
+    roi, vol = kw.pop('dvid_roi', g['roi']), kw.pop('dvid_server', g['volume'])
+    return fplsynapses.roi_to_substacks(vol, None, roi, g['tbars'], int(g['partition_size']), **kw)
+
+
+def check_against_golden(g, out, data_dir, to_host=np.asarray):
+    """the returned volumes and the written files against what the reference wrote"""
+    names = sorted(os.listdir(data_dir))
+    assert [n for n in names if not n.endswith('.npy')] == g['names'].tolist()
+    assert sorted(n[:-4] for n in names if n.endswith('.npy')) == \
+        sorted(n[:-3] for n in g['names'].tolist() if n.endswith('.h5'))
+    for name in g['names'].tolist():
+        path = os.path.join(data_dir, name)
+        if name.endswith('.json'):
+            assert json.load(open(path)) == json.loads(str(g['json.' + name])), name
+            continue
+        h5 = np.asarray(keras_io.read_main(path))
+        npy = np.load(path[:-3] + '.npy')
+        assert h5.dtype == npy.dtype and np.array_equal(h5, npy), name
+        if 'array.' + name in g:
+            assert h5.dtype == np.uint8 and np.array_equal(h5, g['array.' + name]), name
+        else:
+            assert _sha(h5) == str(g['sha.' + name]), name
+    assert [o['id'] for o in out] == g['ids'].tolist()
+    b = int(g['buffer_size'])
+    for o in out:
+        ii, ss = o['id'], o['substack']
+        assert tuple(ss) == tuple(g['substacks'][ii])
+        assert _sha(to_host(o['image'])) == str(g['sha.%03d_im135_48_bf%d.h5' % (ii, b)])
+        assert np.array_equal(to_host(o['roi_mask']), g['array.%03d_bf%d_roimask.h5' % (ii, b)])
+        assert np.array_equal(to_host(o['labels']), g['array.%03d_ru2_ri4_bf%d_labels.h5' % (ii, b)])
+        assert np.array_equal(to_host(o['mask']), g['array.%03d_ru2_ri4_bf%d_mask.h5' % (ii, b)])
+        seg = to_host(o['seg'])
+        assert _sha(seg.view(np.uint64)) == str(g['sha.%03d_seg_bf%d.h5' % (ii, b)])
+        want = g['annot.%d.locs' % ii] - (np.asarray([ss.x, ss.y, ss.z]) - b)
+        assert np.array_equal(np.asarray(o['tbars']['locs']).reshape(-1, 3), want)
+        assert np.array_equal(o['tbars']['conf'], g['annot.%d.conf' % ii])
+
+
+def test_host_roi_to_substacks_writes_what_the_reference_writes(golden, tmp_path, capsys):
+    out = export(golden, str(tmp_path))
+    assert capsys.readouterr().out.split() == [str(i) for i in golden['ids']]
+    check_against_golden(golden, out, str(tmp_path))
+    assert all(isinstance(o[k], np.ndarray) for o in out for k in ('image', 'roi_mask', 'labels', 'mask', 'seg'))
+    assert out[0]['image'].dtype == np.float32 and out[0]['seg'].dtype == np.uint64
+    assert len(out[2]['tbars']['conf']) == 0 and out[2]['labels'].sum() == 0      # the cube with no point
+    # data_dir=None writes nothing; a scalar id; no segmentation
+    one = export(golden, None, substack_ids=int(golden['ids'][0]), seg_name=None)
+    assert len(one) == 1 and one[0]['seg'] is None and np.array_equal(one[0]['mask'], out[0]['mask'])
+
+
+def test_get_substack_annotations_is_the_references(golden):
+    g = golden
+    for ii in g['ids'].tolist():
+        ss = fplutils.szyx(*g['substacks'][ii].tolist())
+        tt = fplsynapses.get_substack_annotations(g['tbars'], g['roi'], ss)
+        assert np.array_equal(tt['locs'].reshape(-1, 3), g['annot.%d.locs' % ii])
+        assert np.array_equal(tt['conf'], g['annot.%d.conf' % ii])
+        box = fplsynapses.get_substack_annotations(g['tbars'], None, ss)
+        lo = np.asarray([ss.x, ss.y, ss.z])
+        want = np.all((g['locs'] >= lo) & (g['locs'] < lo + ss.size), axis=1)
+        assert np.array_equal(box['locs'], g['locs'][want]) and len(box['conf']) >= len(tt['conf'])
+    # the dvid elements the reference reads are read too
+    doc = json.dumps([{'Kind': 'PreSyn', 'Pos': p, 'Prop': {'conf': repr(float(c))}}
+                      for p, c in zip(g['locs'].tolist(), g['conf'])])
+    ss = fplutils.szyx(*g['substacks'][int(g['ids'][0])].tolist())
+    assert np.array_equal(fplsynapses.get_substack_annotations(doc, g['roi'], ss)['locs'],
+                          g['annot.%d.locs' % g['ids'][0]])
+
+
+def test_statistics_mode_prints_the_references_lines(golden, capsys):
+    rows = fplsynapses.roi_to_substacks(golden['volume'], None, golden['roi'], golden['tbars'],
+                                        int(golden['partition_size']))
+    lines = capsys.readouterr().out.splitlines()
+    assert lines == golden['stats'].tolist()
+    assert ['%03d\t%.03f\t%3d' % r for r in rows] == lines
+
+
+def test_the_text_file_and_json_forms(golden, tmp_path):
+    g = golden
+    txt = str(tmp_path / 'roi.txt')
+    with open(txt, 'w') as f_out:
+        f_out.writelines('%d,%d,%d,%d\n' % tuple(r) for r in g['substacks'].tolist())
+    with pytest.raises(ValueError, match='pass the BlockRoi as roi='):
+        export(g, None, dvid_roi=txt)
+    with pytest.raises(ValueError, match='roi= goes with a substack text file'):
+        export(g, None, roi=g['roi'])
+    with pytest.raises(ValueError, match='dvid_roi is a BlockRoi'):
+        export(g, None, dvid_roi='no-such-file')
+    want = export(g, None)
+    js = str(tmp_path / 'roi.json')
+    g['roi'].to_json(js)
+    for got in (export(g, None, dvid_roi=txt, roi=g['roi']),
+                export(g, None, dvid_roi=BlockRoi.from_json(js, int(g['block_size'])))):
+        for a, b in zip(got, want):
+            assert a['substack'] == b['substack']
+            for k in ('image', 'roi_mask', 'labels', 'mask', 'seg'):
+                assert np.array_equal(a[k], b[k])
+    # the file's cubes, not the partition's: a shifted cube list is followed
+    with open(txt, 'w') as f_out:
+        f_out.write('16,8,8,8\n')
+    got = export(g, None, dvid_roi=txt, roi=g['roi'], substack_ids=[0])
+    assert got[0]['substack'] == (16, 8, 8, 8)
+    assert np.array_equal(got[0]['roi_mask'], g['roi'].roi3D((28,) * 3, (2,) * 3))
+    rows = fplsynapses.roi_to_substacks(g['volume'], None, txt, g['tbars'], 2, roi=g['roi'])
+    assert rows[0][1] == g['roi'].voxel_counts([[8, 8, 8, 16, 16, 16]])[0] / 4096.0
+
+
+# ---- full_roi_inference(roi=) -----------------------------------------------------------------------
+
+def test_filter_by_roi_keeps_what_ptquery_keeps():
+    roi, mask, origin = irregular_roi(4)
+    rs = np.random.RandomState(8)
+    locs = rs.rand(300, 3) * 40 - 12                 # (x, y, z), fractional and negative
+    tb = {'locs': locs, 'conf': rs.rand(300)}
+    got = fplpipeline.filter_by_roi(tb, roi)
+    keep = roi.ptquery(np.fliplr(locs).astype('int'))
+    assert 0 < keep.sum() < 300
+    assert np.array_equal(got['locs'], locs[keep]) and np.array_equal(got['conf'], tb['conf'][keep])
+    none = fplpipeline.filter_by_roi({'locs': np.zeros((0, 3)), 'conf': np.zeros(0)}, roi)
+    assert none['locs'].shape == (0, 3)
+
+
+@pytest.mark.gpu
+def test_full_roi_inference_filters_by_the_roi(ctx, tmp_path):
+    from tests.test_pipeline import _small_setup
+    net, vol, cubes = _small_setup()
+    cubes = cubes[:4] + cubes[-1:]
+    kw = dict(obj_min_dist=5, smoothing_sigma=1.5, buffer_sz=10, precision='f32')
+    norm = [128., 33., 0.7]
+    plain = fplobjdetect.full_roi_inference(vol, None, cubes, net, 0.2, str(tmp_path / 'a'), norm, **kw)
+    same = fplobjdetect.full_roi_inference(vol, None, cubes, net, 0.2, str(tmp_path / 'b'), norm,
+                                           roi=None, **kw)
+    assert open(str(tmp_path / 'a/all.p'), 'rb').read() == open(str(tmp_path / 'b/all.p'), 'rb').read()
+    assert np.array_equal(plain['locs'], same['locs'])
+    blocks = np.zeros((5, 6, 5), bool)
+    blocks[0:2, 1:4, 0:3] = True
+    blocks[1, 2, 1] = False
+    roi = BlockRoi.from_block_mask(blocks, block_size=16)
+    got = fplobjdetect.full_roi_inference(vol, None, cubes, net, 0.2, str(tmp_path / 'c'), norm,
+                                          roi=roi, **kw)
+    keep = roi.ptquery(np.fliplr(plain['locs']).astype('int'))
+    assert 0 < keep.sum() < len(keep)
+    assert np.array_equal(got['locs'], plain['locs'][keep]) and np.array_equal(got['conf'], plain['conf'][keep])
+    with open(str(tmp_path / 'c/all.p'), 'rb') as f_in:
+        on_disk = pickle.load(f_in)
+    assert np.array_equal(on_disk['locs'], got['locs']) and np.array_equal(on_disk['conf'], got['conf'])
+
+
+# ---- the build and the C ABI ------------------------------------------------------------------------
+
+def test_the_roi_library_is_a_tenth_table_of_the_build():
+    assert build.ROI_LIBRARIES == (('roi', 'roi', 'fplr', 'fplroi.h', 'libfplroi.so'),)
+    assert build.EXPORT_LIBRARIES == build.PREPARED_LIBRARIES + build.ROI_LIBRARIES
+    walked = build.EXPORT_LIBRARIES
+    assert len({r[0] for r in walked}) == len({r[2] for r in walked}) == len(walked) == 12
+    assert 'ROI_LIBRARIES is a tenth table' in build.__doc__
+    assert _roicapi not in _sidelib.bindings()
+    assert os.path.basename(_roicapi.LIB_PATH) == 'libfplroi.so'
+    for hdr in os.listdir(os.path.join(ROOT, 'include')):
+        if hdr != 'fplroi.h':
+            assert 'fplr_' not in open(os.path.join(ROOT, 'include', hdr)).read(), hdr
+
+
+def test_every_earlier_table_is_unchanged():
+    keys = lambda t: [r[0] for r in t]                              # noqa: E731
+    assert keys(build.SIDE_LIBRARIES) == ['batch', 'mine', 'labels']
+    assert keys(build.ALL_TABLES) == ['batch', 'mine', 'labels', 'plan', 'match', 'near']
+    assert keys(build.EVERY_LIBRARY) == keys(build.ALL_TABLES) + ['assign']
+    assert keys(build.BUILT_LIBRARIES) == keys(build.EVERY_LIBRARY) + ['seg']
+    assert keys(build.LIBRARIES) == keys(build.BUILT_LIBRARIES) + ['merge']
+    assert keys(build.WALKED_LIBRARIES) == keys(build.LIBRARIES) + ['valid']
+    assert keys(build.PREPARED_LIBRARIES) == keys(build.WALKED_LIBRARIES) + ['clahe']
+    for row in build.PREPARED_LIBRARIES:
+        assert row[3] == {'batch': 'fplbatch.h', 'valid': 'fplval.h'}.get(row[0], 'fpl%s.h' % row[0])
+        assert row[4] == 'lib' + row[3][:-2] + '.so'
+
+
+def test_libfplroi_exports_exactly_the_declared_names():
+    if not os.path.exists(_roicapi.LIB_PATH):
+        pytest.skip('libfplroi.so is not built')
+    names = abi.check_exports(_roicapi, 'fplroi.h', 'fplr', N_EXPORTS)
+    assert names == {'fplr_last_error', 'fplr_abi_version', 'fplr_mask_box', 'fplr_ptquery',
+                     'fplr_box_counts', 'fplr_cut_normalize_u8'}
+
+
+def test_every_fplr_entry_point_is_guarded():
+    abi.check_guarded('roi', 'fplroi.h', 'fplr', N_EXPORTS)
+
+
+def test_the_library_loads_and_the_constants_are_the_headers():
+    lib = _roicapi.load_library()
+    assert lib is _roicapi.load_library() and lib.fplr_abi_version() == _roicapi.ABI_VERSION
+    assert issubclass(_roicapi.FplRoiError, RuntimeError)
+    hdr = open(os.path.join(ROOT, 'include', 'fplroi.h')).read()
+    for name in ('ABI_VERSION', 'BLOCK', 'MAX_GRID', 'BLOCK_SIZE_BITS', 'SIDE_BITS', 'COORD_BITS'):
+        assert int(re.search(r'#define FPLR_%s (\d+)' % name, hdr).group(1)) == getattr(_roicapi, name), name
+    from flypylib_amd import roi
+    assert roi.MAX_SIDE == 2 ** _roicapi.SIDE_BITS and roi.MAX_COORD == 2 ** _roicapi.COORD_BITS
+    assert roi.MAX_BLOCK_SIZE == 2 ** _roicapi.BLOCK_SIZE_BITS
+
+
+def test_refusals_before_the_gpu_is_touched():
+    """every refusal here returns before a launch (and before a pointer is looked at)"""
+    err = _roicapi.FplRoiError
+    tables = (4096, 8192, 12288)
+    ok = dict(tables=tables, n_rows=2, n_runs=3, block_size=32, origin=(0, 0, 0), dims=(4, 4, 4),
+              out=16384)
+
+    def mask(**kw):
+        a = dict(ok)
+        a.update(kw)
+        return _roicapi.mask_box(*a.values(), None)
+    with pytest.raises(err, match='fplr_mask_box: null pointer argument'):
+        mask(tables=(0, 8192, 12288))
+    with pytest.raises(err, match='fplr_mask_box: null pointer argument'):
+        mask(out=0)
+    with pytest.raises(err, match=r'n_rows -1 must lie in \[0, 2\^31 - 1\]'):
+        mask(n_rows=-1)
+    with pytest.raises(err, match='1 runs in 2 rows'):
+        mask(n_runs=1)
+    with pytest.raises(err, match=r'block_size 0 must lie in \[1, 2\^20\]'):
+        mask(block_size=0)
+    with pytest.raises(err, match='row_keys is not 8-byte aligned'):
+        mask(tables=(4100, 8192, 12288))
+    with pytest.raises(err, match=r'dims\[1\] 0 must lie in \[1, 2\^21\)'):
+        mask(dims=(4, 0, 4))
+    with pytest.raises(err, match=r'origin\[2\] .* lies outside \+-2\^40'):
+        mask(origin=(0, 0, 2 ** 40))
+    with pytest.raises(err, match='exceeds the 2\\^31 - 1 voxels a box can index'):
+        mask(dims=(2048, 1024, 1024))
+    with pytest.raises(err, match='fplr_ptquery: n -1'):
+        _roicapi.ptquery(tables, 2, 3, 32, 4096, -1, 8192)
+    with pytest.raises(err, match='fplr_ptquery: null pointer argument'):
+        _roicapi.ptquery(tables, 2, 3, 32, 0, 5, 8192)
+    with pytest.raises(err, match='fplr_box_counts: boxes / counts is not 8-byte aligned'):
+        _roicapi.box_counts(tables, 2, 3, 32, 4096, 1, 8196)
+    with pytest.raises(err, match=r'fplr_cut_normalize_u8: extent\[0\] 0'):
+        _roicapi.cut_normalize_u8(4096, (0, 4, 4), (0, 0, 0), (4, 4, 4), 1.0, 2.0, 8192)
+    with pytest.raises(err, match='fplr_cut_normalize_u8: out is not 4-byte aligned'):
+        _roicapi.cut_normalize_u8(4096, (4, 4, 4), (0, 0, 0), (4, 4, 4), 1.0, 2.0, 8194)
+    # n = 0 is answered without a launch and without a look at the pointers
+    _roicapi.ptquery(tables, 2, 3, 32, 0, 0, 0)
+    _roicapi.box_counts(tables, 2, 3, 32, 0, 0, 0)
+
+
+def test_a_missing_library_is_reported_not_replaced_by_the_host(monkeypatch, golden):
+    monkeypatch.setattr(_roicapi._side, '_lib', None)
+    monkeypatch.setattr(_roicapi._side, 'path', '/nonexistent/libfplroi.so')
+    for call in (lambda: golden['roi'].roi3D((4, 4, 4), (0, 0, 0), device=0),
+                 lambda: golden['roi'].ptquery(np.zeros((2, 3), int), device=0),
+                 lambda: golden['roi'].voxel_counts([[0, 0, 0, 4, 4, 4]], device=0),
+                 lambda: export(golden, None, device=0)):
+        with pytest.raises(_roicapi.FplRoiError, match='libfplroi.so not found at /nonexistent') as e:
+            call()
+        assert 'python -m flypylib_amd.csrc.build' in str(e.value) and 'no host fallback' in str(e.value)
+
+
+def test_the_kernels_use_no_atomics_and_divide_exactly():
+    src = open(os.path.join(abi.CSRC, 'roi', 'roi.hip')).read()
+    code = re.sub(r'//.*', '', src)
+    assert 'atomic' not in code.lower()
+    assert '__fdiv_rn(__fsub_rn(' in code and 'fast' not in ' '.join(build.CXXFLAGS)
+    assert 'hipStreamSynchronize' not in code and 'hipDeviceSynchronize' not in code

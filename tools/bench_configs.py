@@ -65,6 +65,11 @@
             the numpy specification on the host (single-threaded by construction, whatever the
             cores), clahe(device=0) from a host array, clahe(device=0) from a resident tensor, and
             the four stages of fplc_clahe alone (HIP events); written to profiles/clahe.json
+  substacks fplsynapses.roi_to_substacks on one 520^3 cube (448 + 2 x 36) with 32 768 T-bars, radii
+            3 / 6, nothing written: numpy on the host, device=0 from a host volume and from a
+            resident one; the four kernels of libfplroi.so alone (HIP events); BlockRoi.voxel_counts
+            over the partition of a 4096^3 ROI on the host and with device=0; written to
+            profiles/substacks.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -864,6 +869,101 @@ def clahe_bench(ctx, torch, n=520, k=64, reps=5):
     return row
 
 
+def substacks_bench(ctx, torch, n_tbars=32768, reps=5, host_reps=2):
+    """fplsynapses.roi_to_substacks on one 520^3 cube (448 + 2 x 36), radii 3 / 6: numpy against
+    device=, the four kernels of libfplroi.so alone, and voxel_counts over a 4096^3 ROI's partition"""
+    from flypylib_amd import _roicapi, fplsynapses, synth
+    from flypylib_amd.roi import BlockRoi
+    dev = torch.device('cuda', ctx.device)
+    side, buf, n = 448, 36, 520
+    vol = synth.em_volume_u8(3, (n, n, n))
+    z, y, x = np.meshgrid(*[np.arange(14)] * 3, indexing='ij')
+    roi = BlockRoi.from_block_mask((z - 6.5) ** 2 + (y - 6.5) ** 2 + (x - 6.5) ** 2 < 60.0)
+    rs = np.random.RandomState(11)
+    tbars = {'locs': rs.randint(0, side, (n_tbars, 3)).astype(np.int64), 'conf': rs.rand(n_tbars)}
+    kw = dict(substack_ids=[0], image_normalize=[128.0, 33.0], buffer_size=buf, radius_use=3, radius_ign=6)
+    row = dict(cube=[n, n, n], substack=side, buffer=buf, tbars=n_tbars, radius_use=3, radius_ign=6,
+               roi_blocks=roi.n_blocks, roi_runs=len(roi.runs),
+               timing='one warm-up, then median / min / max, ms (host: of %d, device: of %d); no files '
+                      'written' % (host_reps, reps))
+
+    def stats(ts):
+        return dict(median=float(np.median(ts)), min=float(min(ts)), max=float(max(ts)))
+
+    def timed(fn, sync, k):
+        ts, r = [], None
+        for i in range(k + 1):
+            t0 = time.perf_counter()
+            r = fn()
+            if sync:
+                torch.cuda.synchronize(dev)
+            if i:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        return stats(ts), r
+
+    def export(source, device):
+        import contextlib
+        import io
+        with contextlib.redirect_stdout(io.StringIO()):
+            return fplsynapses.roi_to_substacks(source, None, roi, tbars, 14, device=device, **kw)[0]
+    row['host_ms'], host = timed(lambda: export(vol, None), False, host_reps)
+    row['device_from_host_ms'], got = timed(lambda: export(vol, ctx.device), True, reps)
+    res = torch.from_numpy(vol).to(dev)
+    row['device_resident_ms'], got_r = timed(lambda: export(res, ctx.device), True, reps)
+    row['tbars_in_roi'] = int(len(host['tbars']['conf']))
+    row['identical'] = bool(all(np.array_equal(host[k].view(np.uint8), got[k].cpu().numpy().view(np.uint8))
+                                and torch.equal(got[k], got_r[k])
+                                for k in ('image', 'roi_mask', 'labels', 'mask')))
+    row['host_over_device_resident'] = row['host_ms']['median'] / row['device_resident_ms']['median']
+    del host, got_r
+
+    # the kernels alone, HIP events
+    tables, stream = roi.device_tables(dev), torch.cuda.current_stream(dev).cuda_stream
+    nr, nk, b = len(roi.row_keys), len(roi.runs), roi.block_size
+    big = BlockRoi.from_block_mask((np.add.outer(np.add.outer((np.arange(128) - 63.5) ** 2,
+                                                              (np.arange(128) - 63.5) ** 2),
+                                                 (np.arange(128) - 63.5) ** 2)) < 62.0 ** 2)
+    cubes = big.partition(16)[0]
+    boxes = np.asarray([(s.z, s.y, s.x, s.size, s.size, s.size) for s in cubes], np.int64)
+    big_tables, boxes_res = big.device_tables(dev), torch.from_numpy(boxes).to(dev)
+    counts = torch.empty(len(boxes), dtype=torch.int64, device=dev)
+    pts = torch.from_numpy(np.fliplr(tbars['locs']).copy()).to(dev)
+    flags = torch.empty(n_tbars, dtype=torch.uint8, device=dev)
+    image, mask = got['image'], got['roi_mask']
+    kernels = {
+        'mask_box': lambda: _roicapi.mask_box(tables, nr, nk, b, (-buf,) * 3, (n,) * 3, mask, stream),
+        'cut_normalize_u8': lambda: _roicapi.cut_normalize_u8(res, (n,) * 3, (-buf,) * 3, (n,) * 3, 128.0,
+                                                              33.0, image, stream),
+        'ptquery': lambda: _roicapi.ptquery(tables, nr, nk, b, pts, n_tbars, flags, stream),
+        'box_counts': lambda: _roicapi.box_counts(big_tables, len(big.row_keys), len(big.runs), 32,
+                                                  boxes_res, len(boxes), counts, stream),
+    }
+    ms = {name: [] for name in kernels}
+    for i in range(reps + 1):
+        for name, fn in kernels.items():
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize(dev)
+            if i:
+                ms[name].append(e0.elapsed_time(e1))
+    row['kernels_ms'] = {name: stats(v) for name, v in ms.items()}
+    row['kernels_timing'] = ('HIP events around one call: mask_box and cut_normalize_u8 on the 520^3 '
+                             'cube, ptquery on %d points, box_counts on the %d cubes of the 4096^3 '
+                             "ROI's partition(16)" % (n_tbars, len(boxes)))
+    row['kernels_bytes'] = {'mask_box': n ** 3, 'cut_normalize_u8': 5 * n ** 3}
+    row['voxel_counts'] = dict(roi='a ball of %d blocks in 128^3 (4096^3 voxels), %d runs'
+                                   % (big.n_blocks, len(big.runs)), cubes=len(boxes))
+    row['voxel_counts']['host_ms'], want = timed(lambda: big.voxel_counts(boxes), False, reps)
+    row['voxel_counts']['device_ms'], cnt = timed(lambda: big.voxel_counts(boxes, device=ctx.device), True,
+                                                  reps)
+    row['voxel_counts']['identical'] = bool(np.array_equal(want, cnt)
+                                            and int(want.sum()) == big.n_blocks * 32 ** 3)
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
@@ -1092,6 +1192,11 @@ def main():
         res['clahe'] = clahe_bench(ctx, torch, a.clahe_size)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'clahe.json')
+
+    if 'substacks' in what:
+        res['substacks'] = substacks_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'substacks.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
