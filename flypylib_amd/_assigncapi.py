@@ -41,7 +41,7 @@ SIGNATURES = {
     'fpla_solve': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplassign.so', 'fpla', FplAssignError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('assign', FplAssignError, SIGNATURES, ABI_VERSION,
                     "the device solver has no host fallback; use solver='host' for scipy's")
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

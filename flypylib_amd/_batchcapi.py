@@ -47,7 +47,7 @@ def _check_structs(lib):
                             % (vb.value, rb.value, VOLUME.itemsize, RECORD.itemsize))
 
 
-_side = SideLibrary('libfplbatch.so', 'fplb', FplBatchError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('batch', FplBatchError, SIGNATURES, ABI_VERSION,
                     'device batch generators have no host fallback; use device=None for the host '
                     'generators', _check_structs)
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check

@@ -29,7 +29,7 @@ SIGNATURES = {
                              _i64, _i32, _vp]),
 }
 
-_side = SideLibrary('libfplclahe.so', 'fplc', FplClaheError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('clahe', FplClaheError, SIGNATURES, ABI_VERSION,
                     'clahe(device=) has no host fallback; use device=None for the numpy executor')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

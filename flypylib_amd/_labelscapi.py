@@ -30,7 +30,7 @@ SIGNATURES = {
                                    _vp, _vp]),
 }
 
-_side = SideLibrary('libfpllabels.so', 'fpll', FplLabelsError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('labels', FplLabelsError, SIGNATURES, ABI_VERSION,
                     'device write_labels_mask has no host fallback; use device=None for the host '
                     'path')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check

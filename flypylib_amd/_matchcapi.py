@@ -33,7 +33,7 @@ SIGNATURES = {
     'fple_pairs_fill': (C.c_int, [_vp, _i64, _vp, _i64, _f64, _vp, _i64, _i64, _vp, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplmatch.so', 'fple', FplMatchError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('match', FplMatchError, SIGNATURES, ABI_VERSION,
                     "device matching has no host fallback; use match='sparse' for the numpy table")
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

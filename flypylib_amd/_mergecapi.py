@@ -47,7 +47,7 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplmerge.so', 'fplg', FplMergeError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('merge', FplMergeError, SIGNATURES, ABI_VERSION,
                     "the device merge has no host fallback; use solver='host' for the host loop")
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

@@ -33,7 +33,7 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplmine.so', 'fplm', FplMineError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('mine', FplMineError, SIGNATURES, ABI_VERSION,
                     'device mining has no host fallback; use device=None for the host path')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

@@ -35,7 +35,7 @@ SIGNATURES = {
     'fpln_pairs_fill': (C.c_int, [_vp, _i64, _f64] + _grid + [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplnear.so', 'fpln', FplNearError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('near', FplNearError, SIGNATURES, ABI_VERSION,
                     "the device table has no host fallback; use method='sparse' without device= "
                     "for the numpy table")
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check

@@ -29,7 +29,7 @@ SIGNATURES = {
     'fplp_plan_bricks': (C.c_int, [_vp, _i64, _dims, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
-_side = SideLibrary('libfplplan.so', 'fplp', FplPlanError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('plan', FplPlanError, SIGNATURES, ABI_VERSION,
                     "planner='device' has no host fallback; use planner='host' for the numpy "
                     'planner')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check

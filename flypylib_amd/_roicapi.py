@@ -32,7 +32,7 @@ SIGNATURES = {
     'fplr_cut_normalize_u8': (C.c_int, [_vp, _pi64, _pi64, _pi64, C.c_float, C.c_float, _vp, _vp]),
 }
 
-_side = SideLibrary('libfplroi.so', 'fplr', FplRoiError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('roi', FplRoiError, SIGNATURES, ABI_VERSION,
                     'BlockRoi(device=) and roi_to_substacks(device=) have no host fallback; use '
                     'device=None for the numpy path')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check

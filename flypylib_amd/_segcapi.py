@@ -29,7 +29,7 @@ SIGNATURES = {
     'fpls_gather_labels': (C.c_int, [_vp, _i32, _pi64, _vp, C.c_int, _i64, _vp, C.c_int, _vp]),
 }
 
-_side = SideLibrary('libfplseg.so', 'fpls', FplSegError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('seg', FplSegError, SIGNATURES, ABI_VERSION,
                     'resident labels have no host fallback; pass a host label array instead')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the side libraries share (csrc/build.py's SIDE_LIBRARIES:
-_batchcapi, _minecapi, _labelscapi): finding and loading the library, binding its
-SIGNATURES, the ABI check, the cache, and turning an rc into the binding's error.
+"""What the ctypes bindings of the side libraries share (one _<key>capi.py per row of
+csrc/build.py's SIDE_LIBRARIES): finding and loading the library, binding its SIGNATURES, the
+ABI check, the cache, and turning an rc into the binding's error.
 
 A binding module declares its constants, its error class and its SIGNATURES, makes one
 SideLibrary of them and keeps `LIB_PATH`, `load_library` and `check` as names of its own.
@@ -9,20 +9,20 @@ import ctypes as C
 import importlib
 import os
 
-LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib')
+from .csrc import build
 
 
 class SideLibrary:
-    """`name`: the file under lib/; `prefix`: of its exports, <prefix>_last_error and
-    <prefix>_abi_version among them; `error`: the RuntimeError subclass the binding raises;
+    """`key`: of its row of build.SIDE_LIBRARIES, which holds the file under lib/ and the prefix
+    of its exports; `error`: the RuntimeError subclass the binding raises;
     `hint`: what the not-found message says of the host path; `post_load(lib)`: a further
     check of a freshly bound library (it raises, or the library is kept)."""
 
-    def __init__(self, name, prefix, error, signatures, abi_version, hint, post_load=None):
-        self.name, self.prefix, self.error = name, prefix, error
-        self.signatures, self.abi_version = signatures, abi_version
+    def __init__(self, key, error, signatures, abi_version, hint, post_load=None):
+        _, _, self.prefix, _, self.name = next(r for r in build.SIDE_LIBRARIES if r[0] == key)
+        self.error, self.signatures, self.abi_version = error, signatures, abi_version
         self.hint, self.post_load = hint, post_load
-        self.path = os.path.join(LIB_DIR, name)
+        self.path = os.path.join(build.LIB_DIR, self.name)
         self._lib = None
 
     def load(self, path=None):
@@ -60,13 +60,12 @@ class SideLibrary:
 
 
 def bindings():
-    """the binding module of every side library the build makes"""
-    from .csrc import build
-    return [importlib.import_module('%s._%scapi' % (__package__, row[0]))
-            for row in build.SIDE_LIBRARIES]
+    """the binding modules of build.EAGER_BINDINGS"""
+    return [importlib.import_module('%s._%scapi' % (__package__, key))
+            for key in build.EAGER_BINDINGS]
 
 
 def load_all():
-    """every side library loads and every declared symbol resolves (no GPU needed)"""
+    """every one of them loads and every declared symbol resolves (no GPU needed)"""
     for binding in bindings():
         binding.load_library()

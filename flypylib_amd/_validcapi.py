@@ -27,7 +27,7 @@ SIGNATURES = {
     'fplv_loss_sums': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
 }
 
-_side = SideLibrary('libfplval.so', 'fplv', FplValidError, SIGNATURES, ABI_VERSION,
+_side = SideLibrary('valid', FplValidError, SIGNATURES, ABI_VERSION,
                     'validation has no host fallback; train without validation_data instead')
 LIB_PATH, load_library, check = _side.path, _side.load, _side.check
 

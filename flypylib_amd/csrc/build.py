@@ -1,5 +1,4 @@
-"""Build libfplhip.so, the side libraries and the stage libraries for gfx950 (MI355X) with
-hipcc, in-tree.
+"""Build libfplhip.so and the side libraries for gfx950 (MI355X) with hipcc, in-tree.
 
     python -m flypylib_amd.csrc.build [--force] [-j N]
 
@@ -16,51 +15,17 @@ prefix only - libfplhip.so's export list stays the fpl_* names of include/fplhip
 side libraries share the headers of csrc/side/ (the C shell of side_abi.h, the device code of
 side_device.h), which are part of their stamps and not of libfplhip.so's.
 
-STAGE_LIBRARIES holds rows of the same shape, built in the same way: libraries that serve a
-stage of a side library rather than a device stage of their own (libfplplan.so plans the
-table libfpllabels.so's kernel reads).  They are a table of their own because SIDE_LIBRARIES
-is also the list of bindings _sidelib.bindings() / load_all() answer for, which stays as it is.
+SIDE_LIBRARIES is the one table of them.  A row is a library's key (its binding is
+flypylib_amd/_<key>capi.py, which reads the library's name and prefix from its row), its source
+directory, its export prefix, its public header and its file under lib/.  build() and
+build_side() walk the table.  Two facts are stated by key beside it:
 
-EVAL_LIBRARIES is a third table of that shape, for what runs after training: libfplmatch.so
-finds the close pairs obj_pr / obj_pr_curve match.  It is no stage of the training round (the
-bindings SIDE_LIBRARIES lists) and serves no side library (STAGE_LIBRARIES), and both of those
-tables are pinned as they stand; its binding loads lazily, when an evaluation asks for a device.
+SHARES_CSRC_HEADERS - libfplseg.so's source shares csrc/seg_box.h with libfplhip.so, so the
+headers of csrc/ are part of its stamp and of no other row's.
 
-POST_LIBRARIES is a fourth table of that shape, for what runs after the pipeline: libfplnear.so
-finds the close pairs within full_roi_inference's point list, which rm_tbar_multi_pred merges.
-The three tables above are pinned by their tests; its binding loads lazily as well.
-
-SOLVE_LIBRARIES is a fifth table of that shape, beside EVAL_LIBRARIES: libfplassign.so solves
-the matching on the pair table libfplmatch.so leaves on the device (solver='device').  The four
-tables above and ALL_TABLES are pinned by their tests, so its row is a table of its own;
-EVERY_LIBRARY is their union.
-
-LABEL_LIBRARIES is a sixth table of that shape, for reads of a resident label volume: libfplseg.so
-gathers the labels of points and pads a box of the volume.  EVERY_LIBRARY is pinned as well, so
-BUILT_LIBRARIES is what build() walks.  Its source shares csrc/seg_box.h with libfplhip.so, so
-the headers of csrc/ are part of its stamp.
-
-MERGE_LIBRARIES is a seventh table of that shape, beside POST_LIBRARIES: libfplmerge.so runs the
-merge loop of rm_tbar_multi_pred on the neighbour table libfplnear.so leaves on the device
-(solver='device').  BUILT_LIBRARIES is pinned too, so LIBRARIES, the union of all seven, is what
-build() walks now.
-
-VALID_LIBRARIES is an eighth table of that shape, for what runs between the epochs of training:
-libfplval.so reduces a batch of inference-mode predictions and its labels to the loss and metric
-sums of held-out validation (FplNetwork.evaluate, the val_ columns).  LIBRARIES is pinned as
-well, so build() and build_side() walk WALKED_LIBRARIES, the union of all eight.
-
-PREP_LIBRARIES is a ninth table of that shape, for what runs before any network sees a volume:
-libfplclahe.so is the per-slice contrast-limited adaptive histogram equalisation of
-fplutils.clahe(device=...).  WALKED_LIBRARIES is pinned too, so build() and build_side() walk
-PREPARED_LIBRARIES, the union of all nine; its binding loads lazily, when a call asks for a device.
-
-ROI_LIBRARIES is a tenth table of that shape, for the first stage of the workflow, the export of
-training substacks: libfplroi.so renders a BlockRoi's mask of a box, answers point queries and
-voxel counts from the ROI's runs, and cuts and normalises a training cube
-(roi.BlockRoi(device=...), fplsynapses.roi_to_substacks(device=...)).  PREPARED_LIBRARIES is pinned
-as well, so build() and build_side() walk EXPORT_LIBRARIES, the union of all ten; its binding loads
-lazily too.
+EAGER_BINDINGS - the bindings _sidelib.bindings() / load_all() answer for, which the driver's
+build check loads: the stages of the training round (batch, mine, labels).  Every other binding
+loads lazily, when a call asks for its device path.
 """
 import argparse
 import hashlib
@@ -80,41 +45,20 @@ SIDE_LIBRARIES = (
     ('batch', 'batchgen', 'fplb', 'fplbatch.h', 'libfplbatch.so'),     # device batch generators
     ('mine', 'mine', 'fplm', 'fplmine.h', 'libfplmine.so'),            # hard-example mining
     ('labels', 'labels', 'fpll', 'fpllabels.h', 'libfpllabels.so'),    # write_labels_mask
-)
-STAGE_LIBRARIES = (
     ('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),            # plan_bricks on the device
-)
-EVAL_LIBRARIES = (
     ('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),        # obj_pr's close pairs
-)
-POST_LIBRARIES = (
     ('near', 'near', 'fpln', 'fplnear.h', 'libfplnear.so'),            # rm_tbar_multi_pred's close pairs
-)
-SOLVE_LIBRARIES = (
     ('assign', 'assign', 'fpla', 'fplassign.h', 'libfplassign.so'),    # obj_pr's matching, solved
-)
-ALL_TABLES = SIDE_LIBRARIES + STAGE_LIBRARIES + EVAL_LIBRARIES + POST_LIBRARIES
-EVERY_LIBRARY = ALL_TABLES + SOLVE_LIBRARIES
-LABEL_LIBRARIES = (
     ('seg', 'seg', 'fpls', 'fplseg.h', 'libfplseg.so'),                # labels of a resident volume
-)
-BUILT_LIBRARIES = EVERY_LIBRARY + LABEL_LIBRARIES
-MERGE_LIBRARIES = (
     ('merge', 'merge', 'fplg', 'fplmerge.h', 'libfplmerge.so'),        # rm_tbar_multi_pred's merge loop
-)
-LIBRARIES = BUILT_LIBRARIES + MERGE_LIBRARIES
-VALID_LIBRARIES = (
     ('valid', 'valid', 'fplv', 'fplval.h', 'libfplval.so'),            # held-out validation's sums
-)
-WALKED_LIBRARIES = LIBRARIES + VALID_LIBRARIES
-PREP_LIBRARIES = (
     ('clahe', 'clahe', 'fplc', 'fplclahe.h', 'libfplclahe.so'),        # fplutils.clahe
-)
-PREPARED_LIBRARIES = WALKED_LIBRARIES + PREP_LIBRARIES
-ROI_LIBRARIES = (
     ('roi', 'roi', 'fplr', 'fplroi.h', 'libfplroi.so'),                # BlockRoi, roi_to_substacks
 )
-EXPORT_LIBRARIES = PREPARED_LIBRARIES + ROI_LIBRARIES
+# the rows whose sources include headers of csrc/ itself (seg_box.h), by key
+SHARES_CSRC_HEADERS = ('seg',)
+# the rows whose bindings _sidelib.load_all() loads, by key; the others load lazily
+EAGER_BINDINGS = ('batch', 'mine', 'labels')
 ARCH = 'gfx950'
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 CXXFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC',
@@ -232,24 +176,22 @@ def build(force=False, jobs=4, verbose=True):
     _build_library(LIB, 'fpl_*', _sources(), HERE,
                    _digest(_local_headers(HERE) + [os.path.join(inc, 'fplhip.h')]),
                    force, jobs, verbose)
-    for row in EXPORT_LIBRARIES:
+    for row in SIDE_LIBRARIES:
         build_side(row[0], force, jobs, verbose)
     return LIB
 
 
 def build_side(key, force=False, jobs=4, verbose=True):
-    """one row of SIDE_LIBRARIES, STAGE_LIBRARIES, EVAL_LIBRARIES, POST_LIBRARIES,
-    SOLVE_LIBRARIES, LABEL_LIBRARIES, MERGE_LIBRARIES, VALID_LIBRARIES, PREP_LIBRARIES or
-    ROI_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that exports the row's prefix only"""
-    row = next(r for r in EXPORT_LIBRARIES if r[0] == key)
-    _, sub, prefix, header, lib = row
+    """one row of SIDE_LIBRARIES: same flags, same SHA-stamped rebuild, a version script that
+    exports the row's prefix only"""
+    _, sub, prefix, header, lib = next(r for r in SIDE_LIBRARIES if r[0] == key)
     src_dir, inc = os.path.join(HERE, sub), os.path.join(ROOT, 'include')
     srcs = [(f, '%s_%s' % (sub, f[:-4]), ['-I' + inc])
             for f in sorted(os.listdir(src_dir)) if f.endswith('.hip')]
     return _build_library(os.path.join(LIB_DIR, lib), prefix + '_*', srcs, src_dir,
                           _digest(_local_headers(src_dir)
                                   + _local_headers(os.path.join(HERE, 'side'))
-                                  + (_local_headers(HERE) if row in LABEL_LIBRARIES else [])
+                                  + (_local_headers(HERE) if key in SHARES_CSRC_HEADERS else [])
                                   + [os.path.join(inc, header)]),
                           force, jobs, verbose)
 

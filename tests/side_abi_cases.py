@@ -1,6 +1,5 @@
-"""The C ABI checks every side library gets (test_batchgen_plan.py, test_mine_host.py,
-test_labels_host.py): the export list is what the public header declares, and every entry
-point is a guarded function-try-block."""
+"""The C ABI checks every side library gets (test_side_libraries.py): the export list is what
+the public header declares, and every entry point is a guarded function-try-block."""
 import os
 import re
 import shutil

@@ -2,20 +2,18 @@
 solve_component was factored out against the recorded results of the commit before, the
 solver= keyword of the public calls, the one-optimum property of every case test_gpu_assign.py
 and test_gpu_assign_stages.py compare matrix for matrix, the paths the shapes of
-test_gpu_assign_stages.py are chosen to reach, the fifth table of the build and the C ABI of
-libfplassign.so."""
+test_gpu_assign_stages.py are chosen to reach, and what is libfplassign.so's own of its C ABI
+(the rest is tests/test_side_libraries.py's)."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from flypylib_amd import _assigncapi, _matchcapi, _sidelib, fplobjdetect, match
-from flypylib_amd.csrc import build
-from tests import assign_cases as ac, match_cases as cases, side_abi_cases as abi
+from flypylib_amd import _assigncapi, fplobjdetect, match
+from tests import assign_cases as ac, match_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_EXPORTS = 10
 T = ac.T
 
 
@@ -476,43 +474,11 @@ def test_the_integer_rods_hold_equal_costs(case):
         assert min(f[4] for f in found) == 0.0                        # and optima that tie exactly
 
 
-# ---- the build and the C ABI ---------------------------------------------------------------------
+# ---- the C ABI ------------------------------------------------------------------------------------
 
-def test_libfplassign_exports_exactly_the_declared_names():
-    names = abi.check_exports(_assigncapi, 'fplassign.h', 'fpla', N_EXPORTS)
-    assert names == {'fpla_last_error', 'fpla_abi_version', 'fpla_scratch_bytes', 'fpla_flags_count',
-                     'fpla_flags_fill', 'fpla_conf_flags', 'fpla_boundaries', 'fpla_pair_costs',
-                     'fpla_labels', 'fpla_solve'}
-
-
-def test_every_fpla_entry_point_is_guarded():
-    abi.check_guarded('assign', 'fplassign.h', 'fpla', N_EXPORTS)
-
-
-def test_the_solver_is_a_fifth_table_of_the_build():
-    assert build.SOLVE_LIBRARIES == (('assign', 'assign', 'fpla', 'fplassign.h', 'libfplassign.so'),)
-    assert build.EVERY_LIBRARY == build.ALL_TABLES + build.SOLVE_LIBRARIES
-    assert build.EVAL_LIBRARIES == (('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),)
-    assert _assigncapi not in _sidelib.bindings()
-    assert os.path.basename(_assigncapi.LIB_PATH) == 'libfplassign.so'
-    assert 'SOLVE_LIBRARIES is a fifth table' in build.__doc__
-    # libfplmatch.so keeps its names, and no other library spells this one's
-    assert abi.declared('fplmatch.h', 'fple') == set(_matchcapi.SIGNATURES) and len(_matchcapi.SIGNATURES) == 5
-    for hdr in os.listdir(os.path.join(ROOT, 'include')):
-        if hdr != 'fplassign.h':
-            assert 'fpla_' not in open(os.path.join(ROOT, 'include', hdr)).read(), hdr
-
-
-def test_the_library_loads_and_every_symbol_resolves():
-    lib = _assigncapi.load_library()
-    assert lib is _assigncapi.load_library()
-    assert lib.fpla_abi_version() == _assigncapi.ABI_VERSION
-    for name, (res, args) in _assigncapi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
+def test_the_constants_are_the_headers_and_the_hint_names_the_host_solver():
     with pytest.raises(_assigncapi.FplAssignError) as e:
         _assigncapi.load_library('/nonexistent/x.so')
-    assert str(e.value).startswith('libfplassign.so not found at /nonexistent/x.so')
     assert 'no host fallback' in str(e.value) and "solver='host'" in str(e.value)
     hdr = open(os.path.join(ROOT, 'include', 'fplassign.h')).read()
     for name, value in (('ABI_VERSION', _assigncapi.ABI_VERSION), ('BLOCK', _assigncapi.BLOCK),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from flypylib_amd import _batchcapi, batchgen, fplobjdetect
-from tests import batchgen_cases as cases, side_abi_cases as abi
+from tests import batchgen_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,15 +81,6 @@ def test_records_are_the_c_struct():
     # arguments are checked first)
     with pytest.raises(_batchcapi.FplBatchError, match='null pointer'):
         _batchcapi.gather(0, 1, 0, 1, (8, 8, 8), _batchcapi.F32, False, 0, 0, 0, 0)
-
-
-def test_libfplbatch_exports_exactly_the_declared_names():
-    declared = abi.check_exports(_batchcapi, 'fplbatch.h', 'fplb', 4)
-    assert not any(n.startswith('fpl_') for n in declared)
-
-
-def test_every_fplb_entry_point_is_guarded():
-    abi.check_guarded('batchgen', 'fplbatch.h', 'fplb', 4)
 
 
 def test_device_mode_refuses_what_it_does_not_take():

@@ -8,11 +8,10 @@ import numpy as np
 import pytest
 
 from flypylib_amd import _labelscapi, fplsynapses, labels
-from tests import labels_cases as cases, side_abi_cases as abi
+from tests import labels_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'synapses.npz'))
-N_EXPORTS = 3
 
 
 def _host(tbars, roi, ru, ri, buf):
@@ -156,10 +155,6 @@ def test_plan_bricks_lists_every_pair_whose_cube_meets_the_brick(shape, half, br
 
 # ---- the C ABI of libfpllabels.so ---------------------------------------------------------------
 
-def test_libfpllabels_exports_exactly_the_declared_names():
-    abi.check_exports(_labelscapi, 'fpllabels.h', 'fpll', N_EXPORTS)
-
-
 def test_the_other_libraries_keep_their_export_lists():
     """the labels entry points live in a library of their own"""
     for hdr in ('fplhip.h', 'fplbatch.h', 'fplmine.h'):
@@ -169,10 +164,6 @@ def test_the_other_libraries_keep_their_export_lists():
         for f in os.listdir(d):
             if f.endswith(('.hip', '.h')):
                 assert 'fpll_' not in open(os.path.join(d, f)).read(), f
-
-
-def test_every_fpll_entry_point_is_guarded():
-    abi.check_guarded('labels', 'fpllabels.h', 'fpll', N_EXPORTS)
 
 
 def test_refused_calls_leave_a_message_and_touch_no_gpu():

@@ -1,18 +1,16 @@
 """The device planner of write_labels_mask, host side (no GPU): labels.plan_pairs against
-labels.plan_bricks, the planner keyword of the public call, the second table of the build and
-the C ABI of libfplplan.so."""
+labels.plan_bricks, the planner keyword of the public call and what is libfplplan.so's own of
+its C ABI (the rest is tests/test_side_libraries.py's)."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from flypylib_amd import _labelscapi, _plancapi, _sidelib, fplsynapses, labels
-from flypylib_amd.csrc import build
-from tests import labels_cases as cases, side_abi_cases as abi
+from flypylib_amd import _labelscapi, _plancapi, fplsynapses, labels
+from tests import labels_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_EXPORTS = 4
 
 
 @pytest.mark.parametrize('i', range(len(cases.RULE_CASES)))
@@ -52,26 +50,7 @@ def test_the_planner_keyword_is_checked_by_name():
     assert labels.PLANNERS == ('host', 'device')
 
 
-def test_the_planner_is_a_stage_library_of_the_build():
-    assert [r[0] for r in build.SIDE_LIBRARIES] == ['batch', 'mine', 'labels']
-    assert all(len(r) == 5 for r in build.SIDE_LIBRARIES + build.STAGE_LIBRARIES)
-    assert build.STAGE_LIBRARIES == (('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),)
-    assert _plancapi not in _sidelib.bindings() and len(_sidelib.bindings()) == 3
-    assert os.path.basename(_plancapi.LIB_PATH) == 'libfplplan.so'
-    assert os.path.dirname(_plancapi.LIB_PATH) == os.path.dirname(_labelscapi.LIB_PATH)
-
-
 # ---- the C ABI of libfplplan.so -----------------------------------------------------------------
-
-def test_libfplplan_exports_exactly_the_declared_names():
-    names = abi.check_exports(_plancapi, 'fplplan.h', 'fplp', N_EXPORTS)
-    assert names == {'fplp_last_error', 'fplp_abi_version', 'fplp_scratch_bytes',
-                     'fplp_plan_bricks'}
-
-
-def test_every_fplp_entry_point_is_guarded():
-    abi.check_guarded('plan', 'fplplan.h', 'fplp', N_EXPORTS)
-
 
 def test_the_other_libraries_keep_their_export_lists():
     """the planner's entry points live in a library of their own"""
@@ -85,18 +64,7 @@ def test_the_other_libraries_keep_their_export_lists():
                 assert 'fplp_' not in open(os.path.join(d, f)).read(), f
 
 
-def test_the_library_loads_and_every_symbol_resolves():
-    lib = _plancapi.load_library()
-    assert lib is _plancapi.load_library()
-    assert lib.fplp_abi_version() == _plancapi.ABI_VERSION
-    for name, (res, args) in _plancapi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert issubclass(_plancapi.FplPlanError, RuntimeError)
-    with pytest.raises(_plancapi.FplPlanError) as e:
-        _plancapi.load_library('/nonexistent/x.so')
-    assert str(e.value).startswith('libfplplan.so not found at /nonexistent/x.so')
-    assert 'python -m flypylib_amd.csrc.build' in str(e.value) and 'no host fallback' in str(e.value)
+def test_the_constants_are_the_headers():
     hdr = open(os.path.join(ROOT, 'include', 'fplplan.h')).read()
     assert int(re.search(r'#define FPLP_ABI_VERSION (\d+)', hdr).group(1)) == _plancapi.ABI_VERSION
     assert tuple(int(re.search(r'#define FPLP_BRICK_%s (\d+)' % a, hdr).group(1))

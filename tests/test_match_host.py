@@ -1,6 +1,6 @@
 """Sparse matching, host side (no GPU): match.pairs_numpy / pair_costs / match_sparse against
-the dense obj_pr and obj_match, the match= keyword of the public calls, the third table of the
-build and the C ABI of libfplmatch.so."""
+the dense obj_pr and obj_match, the match= keyword of the public calls and what is
+libfplmatch.so's own of its C ABI (the rest is tests/test_side_libraries.py's)."""
 import ctypes as C
 import os
 import re
@@ -8,12 +8,10 @@ import re
 import numpy as np
 import pytest
 
-from flypylib_amd import _matchcapi, _sidelib, fplobjdetect, match
-from flypylib_amd.csrc import build
-from tests import match_cases as cases, side_abi_cases as abi
+from flypylib_amd import _matchcapi, fplobjdetect, match
+from tests import match_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_EXPORTS = 5
 T = cases.T
 
 
@@ -33,16 +31,6 @@ POINT_SETS = dict(_point_sets())
 
 # ---- the C ABI of libfplmatch.so ----------------------------------------------------------------
 
-def test_libfplmatch_exports_exactly_the_declared_names():
-    names = abi.check_exports(_matchcapi, 'fplmatch.h', 'fple', N_EXPORTS)
-    assert names == {'fple_last_error', 'fple_abi_version', 'fple_scratch_bytes',
-                     'fple_pairs_count', 'fple_pairs_fill'}
-
-
-def test_every_fple_entry_point_is_guarded():
-    abi.check_guarded('match', 'fplmatch.h', 'fple', N_EXPORTS)
-
-
 def test_the_other_libraries_keep_their_export_lists():
     """the matching entry points live in a library of their own"""
     for hdr in ('fplhip.h', 'fplbatch.h', 'fplmine.h', 'fpllabels.h', 'fplplan.h'):
@@ -54,28 +42,7 @@ def test_the_other_libraries_keep_their_export_lists():
                 assert 'fple_' not in open(os.path.join(d, f)).read(), f
 
 
-def test_matching_is_a_third_table_of_the_build():
-    assert [r[0] for r in build.SIDE_LIBRARIES] == ['batch', 'mine', 'labels']
-    assert build.STAGE_LIBRARIES == (('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),)
-    assert build.EVAL_LIBRARIES == (('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),)
-    assert all(len(r) == 5 for r in build.EVAL_LIBRARIES)
-    assert _matchcapi not in _sidelib.bindings() and len(_sidelib.bindings()) == 3
-    assert os.path.basename(_matchcapi.LIB_PATH) == 'libfplmatch.so'
-    assert 'EVAL_LIBRARIES is a third table' in build.__doc__
-
-
-def test_the_library_loads_and_every_symbol_resolves():
-    lib = _matchcapi.load_library()
-    assert lib is _matchcapi.load_library()
-    assert lib.fple_abi_version() == _matchcapi.ABI_VERSION
-    for name, (res, args) in _matchcapi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert issubclass(_matchcapi.FplMatchError, RuntimeError)
-    with pytest.raises(_matchcapi.FplMatchError) as e:
-        _matchcapi.load_library('/nonexistent/x.so')
-    assert str(e.value).startswith('libfplmatch.so not found at /nonexistent/x.so')
-    assert 'python -m flypylib_amd.csrc.build' in str(e.value) and 'no host fallback' in str(e.value)
+def test_the_constants_are_the_headers():
     hdr = open(os.path.join(ROOT, 'include', 'fplmatch.h')).read()
     for name, value in (('ABI_VERSION', _matchcapi.ABI_VERSION), ('BLOCK', _matchcapi.BLOCK),
                         ('TILE', _matchcapi.TILE), ('MAX_SEGMENTS', _matchcapi.MAX_SEGMENTS),

@@ -10,12 +10,11 @@ import re
 import numpy as np
 import pytest
 
-from flypylib_amd import _mergecapi, _nearcapi, _sidelib, dedupe, fplpipeline, fplsynapses, near
+from flypylib_amd import _mergecapi, _nearcapi, dedupe, fplpipeline, fplsynapses, near
 from flypylib_amd.csrc import build
 from tests import merge_cases as mc, near_cases, side_abi_cases as abi
 
 ROOT = abi.ROOT
-N_EXPORTS = 11
 T = near_cases.T
 CASES = mc.all_cases()
 _SPARSE = {}
@@ -205,35 +204,9 @@ def test_a_missing_library_is_reported_before_a_missing_gpu(monkeypatch):
 
 # ---- the C ABI and the build -----------------------------------------------------------------------
 
-def test_libfplmerge_exports_exactly_the_declared_names():
-    names = abi.check_exports(_mergecapi, 'fplmerge.h', 'fplg', N_EXPORTS)
-    assert {'fplg_rows_count', 'fplg_labels', 'fplg_group_keys', 'fplg_flags_fill', 'fplg_solve'} <= names
-
-
-def test_every_fplg_entry_point_is_guarded():
-    abi.check_guarded('merge', 'fplmerge.h', 'fplg', N_EXPORTS)
-
-
-def test_the_merge_library_is_a_seventh_table_of_the_build():
-    assert build.MERGE_LIBRARIES == (('merge', 'merge', 'fplg', 'fplmerge.h', 'libfplmerge.so'),)
-    assert build.LIBRARIES == build.BUILT_LIBRARIES + build.MERGE_LIBRARIES and len(build.LIBRARIES) == 9
-    assert len({r[0] for r in build.LIBRARIES}) == len({r[2] for r in build.LIBRARIES}) == 9
-    assert _mergecapi not in _sidelib.bindings() and os.path.basename(_mergecapi.LIB_PATH) == 'libfplmerge.so'
-    assert 'MERGE_LIBRARIES is a seventh table' in build.__doc__
-    # libfplnear.so's ABI is what it was
-    assert _nearcapi.ABI_VERSION == 1 and len(_nearcapi.SIGNATURES) == 6
-    for hdr in os.listdir(os.path.join(ROOT, 'include')):
-        if hdr != 'fplmerge.h':
-            assert 'fplg_' not in open(os.path.join(ROOT, 'include', hdr)).read(), hdr
-
-
 def test_the_library_loads_and_the_constants_are_the_headers():
-    lib = _mergecapi.load_library()
-    assert lib is _mergecapi.load_library() and lib.fplg_abi_version() == _mergecapi.ABI_VERSION
-    for name, (res, args) in _mergecapi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert issubclass(_mergecapi.FplMergeError, RuntimeError)
+    assert _mergecapi.load_library().fplg_abi_version() == _mergecapi.ABI_VERSION
+    assert _nearcapi.ABI_VERSION == 1                                # libfplnear.so's ABI is what it was
     hdr = open(os.path.join(ROOT, 'include', 'fplmerge.h')).read()
     for name in ('ABI_VERSION', 'BLOCK', 'MAX_BLOCKS', 'SCAN_THREADS', 'SOLVE_BLOCK', 'SOLVE_BLOCKS',
                  'CAND_CAP', 'COMP_CAP', 'MAX_MOVES'):

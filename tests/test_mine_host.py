@@ -8,17 +8,11 @@ import numpy as np
 import pytest
 
 from flypylib_amd import FplNetwork, _minecapi, batchgen, fplobjdetect, mine
-from tests import batchgen_cases as cases, side_abi_cases as abi
+from tests import batchgen_cases as cases
 from tests import mine_cases
 from tests.mine_cases import mining_case as _mining_case, ulp_distance as _ulp_distance
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_EXPORTS = 5
-
-
-def test_libfplmine_exports_exactly_the_declared_names():
-    declared = abi.check_exports(_minecapi, 'fplmine.h', 'fplm', N_EXPORTS)
-    assert not any(n.startswith(('fpl_', 'fplb_')) for n in declared)
 
 
 def test_the_other_libraries_keep_their_export_lists():
@@ -29,10 +23,6 @@ def test_the_other_libraries_keep_their_export_lists():
     for f in os.listdir(csrc):
         if f.endswith(('.hip', '.h')):
             assert 'fplm_' not in open(os.path.join(csrc, f)).read(), f
-
-
-def test_every_fplm_entry_point_is_guarded():
-    abi.check_guarded('mine', 'fplmine.h', 'fplm', N_EXPORTS)
 
 
 def test_refused_calls_leave_a_message_and_touch_no_gpu():

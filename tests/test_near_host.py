@@ -8,12 +8,11 @@ import tracemalloc
 import numpy as np
 import pytest
 
-from flypylib_amd import _matchcapi, _nearcapi, _sidelib, near
+from flypylib_amd import _matchcapi, _nearcapi, near
 from flypylib_amd.csrc import build
 from tests import near_cases as cases, side_abi_cases as abi
 
 ROOT = abi.ROOT
-N_EXPORTS = 6
 T = cases.T
 
 
@@ -106,16 +105,6 @@ def test_cell_side_keeps_partners_within_one_cell():
 
 # ---- the C ABI of libfplnear.so ----------------------------------------------------------------
 
-def test_libfplnear_exports_exactly_the_declared_names():
-    names = abi.check_exports(_nearcapi, 'fplnear.h', 'fpln', N_EXPORTS)
-    assert names == {'fpln_last_error', 'fpln_abi_version', 'fpln_scratch_bytes', 'fpln_cell_keys',
-                     'fpln_pairs_count', 'fpln_pairs_fill'}
-
-
-def test_every_fpln_entry_point_is_guarded():
-    abi.check_guarded('near', 'fplnear.h', 'fpln', N_EXPORTS)
-
-
 def test_the_other_libraries_keep_their_export_lists():
     for hdr in ('fplhip.h', 'fplbatch.h', 'fplmine.h', 'fpllabels.h', 'fplplan.h', 'fplmatch.h'):
         assert 'fpln_' not in open(os.path.join(ROOT, 'include', hdr)).read()
@@ -127,29 +116,7 @@ def test_the_other_libraries_keep_their_export_lists():
     assert abi.declared('fplmatch.h', 'fple') == set(_matchcapi.SIGNATURES) and len(_matchcapi.SIGNATURES) == 5
 
 
-def test_the_neighbour_table_is_a_fourth_table_of_the_build():
-    assert [r[0] for r in build.SIDE_LIBRARIES] == ['batch', 'mine', 'labels']
-    assert build.STAGE_LIBRARIES == (('plan', 'plan', 'fplp', 'fplplan.h', 'libfplplan.so'),)
-    assert build.EVAL_LIBRARIES == (('match', 'match', 'fple', 'fplmatch.h', 'libfplmatch.so'),)
-    assert build.POST_LIBRARIES == (('near', 'near', 'fpln', 'fplnear.h', 'libfplnear.so'),)
-    assert build.ALL_TABLES[-1] == build.POST_LIBRARIES[0] and len(build.ALL_TABLES) == 6
-    assert _nearcapi not in _sidelib.bindings() and len(_sidelib.bindings()) == 3
-    assert os.path.basename(_nearcapi.LIB_PATH) == 'libfplnear.so'
-    assert 'POST_LIBRARIES is a fourth table' in build.__doc__
-
-
-def test_the_library_loads_and_every_symbol_resolves():
-    lib = _nearcapi.load_library()
-    assert lib is _nearcapi.load_library()
-    assert lib.fpln_abi_version() == _nearcapi.ABI_VERSION
-    for name, (res, args) in _nearcapi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    assert issubclass(_nearcapi.FplNearError, RuntimeError)
-    with pytest.raises(_nearcapi.FplNearError) as e:
-        _nearcapi.load_library('/nonexistent/x.so')
-    assert str(e.value).startswith('libfplnear.so not found at /nonexistent/x.so')
-    assert 'python -m flypylib_amd.csrc.build' in str(e.value) and 'no host fallback' in str(e.value)
+def test_the_constants_are_the_headers():
     hdr = open(os.path.join(ROOT, 'include', 'fplnear.h')).read()
     for name, value in (('ABI_VERSION', _nearcapi.ABI_VERSION), ('BLOCK', _nearcapi.BLOCK),
                         ('SCAN_THREADS', _nearcapi.SCAN_THREADS),

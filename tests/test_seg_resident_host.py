@@ -23,27 +23,17 @@ def test_seg_origin_needs_a_resident_seg():
 
 
 def test_the_new_entry_points_are_bound():
-    """libfplseg.so is built, exports what include/fplseg.h declares and nothing else, and the box
-    descriptor of fpl_v2o_set_seg has the header's layout"""
+    """libfplseg.so is built at the header's ABI version (what it exports is
+    tests/test_side_libraries.py's), and the box descriptor of fpl_v2o_set_seg has the header's
+    layout"""
     import os
     import re
-    import shutil
-    import subprocess
     from flypylib_amd import _segcapi
-    from flypylib_amd.csrc import build
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hdr = open(os.path.join(root, 'include', 'fplseg.h')).read()
-    declared = set(re.findall(r'\b(fpls_[a-z0-9_]+)\s*\(', hdr))
-    assert declared == set(_segcapi.SIGNATURES) and len(declared) == 4
     lib = _segcapi.load_library()
     assert lib.fpls_abi_version() == _segcapi.ABI_VERSION == int(
         re.search(r'#define FPLS_ABI_VERSION (\d+)', hdr).group(1))
-    if shutil.which('nm'):
-        out = subprocess.run(['nm', '-D', '--defined-only', _segcapi.LIB_PATH], check=True,
-                             stdout=subprocess.PIPE, text=True).stdout
-        assert {ln.split()[-1] for ln in out.splitlines() if ln.strip()} == declared
-    assert build.LABEL_LIBRARIES == (('seg', 'seg', 'fpls', 'fplseg.h', 'libfplseg.so'),)
-    assert build.BUILT_LIBRARIES == build.EVERY_LIBRARY + build.LABEL_LIBRARIES
     # every entry point is a function-try-block closed by FPLS_CATCH
     src = open(os.path.join(root, 'flypylib_amd', 'csrc', 'seg', 'seg.hip')).read()
     assert len(re.findall(r'^FPLS_EXPORT int fpls_\w+\([^{]*\) try \{', src, re.M)) == 3
