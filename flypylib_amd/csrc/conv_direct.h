@@ -1,4 +1,4 @@
-// Direct fp32 conv kernel shared by the per-op inference executor (generic.hip)
+// Direct fp32 conv / transposed-conv kernels shared by the per-op inference executor (generic.hip)
 // and the training engine (train.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,3 +52,25 @@ static __global__ __launch_bounds__(256) void conv3d_direct_f32(
       yp[j] = apply_act(fmaf(acc[j], scale[co0 + j], shift[co0 + j]), act);
 }
 
+// Direct Conv3DTranspose(cout, 2, strides=2, 'valid'): the readable restatement of
+// FPL_OP_DECONV.  One thread = one output element; its parity (a, b, c) picks the tap, the
+// input voxel is the output voxel halved.  x (n, D, H, W, cin), w [8][cout][cin],
+// y (n, 2D, 2H, 2W, cout).
+static __global__ __launch_bounds__(256) void deconv2_direct_f32(
+    const float *__restrict__ x, const float *__restrict__ w,
+    const float *__restrict__ scale, const float *__restrict__ shift,
+    float *__restrict__ y, int64_t n_out, int D, int H, int W, int cin, int cout, int act) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  int64_t t = i;
+  const int co = (int)(t % cout); t /= cout;
+  const int ox = (int)(t % (2 * W)); t /= 2 * W;
+  const int oy = (int)(t % (2 * H)); t /= 2 * H;
+  const int oz = (int)(t % (2 * D)); t /= 2 * D;
+  const int tap = ((oz & 1) * 2 + (oy & 1)) * 2 + (ox & 1);
+  const float *xp = x + ((((t * D + (oz >> 1)) * H + (oy >> 1)) * (int64_t)W + (ox >> 1)) * cin);
+  const float *wp = w + ((int64_t)tap * cout + co) * cin;
+  float acc = 0.f;
+  for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[ci], acc);
+  y[i] = apply_act(fmaf(acc, scale[co], shift[co]), act);
+}

@@ -874,6 +874,136 @@ __global__ __launch_bounds__(256) void stem_conv1_pool_f32(StemF a) {
   }
 }
 
+// ---- Conv3DTranspose(cout, 2, strides 2, 'valid') as a voxel GEMM (fp32) --------------
+// No two taps overlap: M = input voxels, K = cin, N = 8 * cout.  N is ordered
+// [a][b][c][co] (z, y, x parity, channel): in the channels-last output the two x parities of
+// one input voxel are adjacent - 2 * cout consecutive floats - and consecutive input voxels of
+// an x row continue that run, so for each of the four (a, b) output rows a wave's 16 * G
+// voxels fill ONE contiguous piece of 16 * G * 2 * cout floats.  The weights are the A
+// operand (rows = N), the voxels the B operand: lane (c, g) ends up with four consecutive N
+// of voxel c - one 16-B store when cout is even.  Per input voxel the kernel reads cin floats
+// and writes 8 * cout: it is bound by its stores.
+// NKB > 0 (cin <= 48; four K-blocks in registers spilled scalar registers): cin <= 16 * NKB
+// and the G x NKB input quads of a lane stay in registers for all
+// 4 * nb2 N-blocks; NKB = 0: any cin, the quads are re-read (from L1) per N-block.
+struct DeconvF {
+  const float *in; int64_t M; int cin;     // (n, D, H, W, cin); M = n * D * H * W
+  int D, H, W;
+  const float *w;                          // fragments [ab][nb][kb][lane][4], scale folded in
+  const float *shift;                      // [16 * nb2] by N index inside an (a, b) row
+  int act;
+  float *out; int cout;                    // (n, 2D, 2H, 2W, cout)
+  int nb2;                                 // N-blocks per (a, b) row: ceil(2 * cout / 16)
+};
+
+// four consecutive input channels of voxel m from `ch` on, zero beyond cin; no divergent
+// branch: a lane outside reads a valid address of its voxel and drops the value
+__device__ __forceinline__ f32x4 load_in_quad(const float *in, int64_t m, int cin, int ch) {
+  const float *row = in + m * cin;
+  f32x4 bf;
+  if ((cin & 3) == 0) {                    // wave-uniform: quads never straddle cin
+    const bool inside = ch < cin;
+    bf = *reinterpret_cast<const f32x4 *>(row + (inside ? ch : 0));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bf[q] = inside ? bf[q] : 0.f;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool inside = ch + q < cin;
+      const float v = row[inside ? ch + q : 0];
+      bf[q] = inside ? v : 0.f;
+    }
+  }
+  return bf;
+}
+
+template <int NKB, int G>
+__global__ __launch_bounds__(256) void deconv2_f32(DeconvF a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int nkb = NKB ? NKB : (a.cin + 15) / 16;
+  const int N2 = 2 * a.cout;
+  const int64_t row = (int64_t)2 * a.W * a.cout;          // floats per output x row
+  const int64_t groups = (a.M + 16 * G - 1) / (16 * G);
+  for (int64_t grp = (int64_t)blockIdx.x * 4 + wave; grp < groups; grp += (int64_t)gridDim.x * 4) {
+    int64_t m[G], obase[G];
+    bool ok[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      int64_t mm = (grp * G + q) * 16 + c;
+      ok[q] = mm < a.M;
+      mm = ok[q] ? mm : a.M - 1;
+      m[q] = mm;
+      int64_t t = mm;
+      const int x = (int)(t % a.W); t /= a.W;
+      const int y = (int)(t % a.H); t /= a.H;
+      const int z = (int)(t % a.D); t /= a.D;
+      obase[q] = ((t * (2 * a.D) + 2 * z) * (2 * a.H) + 2 * y) * row + (int64_t)2 * x * a.cout;
+    }
+    f32x4 bf[G][NKB ? NKB : 1];
+    if (NKB) {
+#pragma unroll
+      for (int q = 0; q < G; ++q)
+#pragma unroll
+        for (int kb = 0; kb < (NKB ? NKB : 1); ++kb) bf[q][kb] = load_in_quad(a.in, m[q], a.cin, 16 * kb + 4 * g);
+    }
+#pragma unroll 1
+    for (int ab = 0; ab < 4; ++ab) {
+      const int64_t aboff = ((int64_t)(ab >> 1) * (2 * a.H) + (ab & 1)) * row;
+#pragma unroll 1
+      for (int nb = 0; nb < a.nb2; ++nb) {
+        const f32x4 sh = *reinterpret_cast<const f32x4 *>(a.shift + 16 * nb + 4 * g);
+        f32x4 acc[G];
+#pragma unroll
+        for (int q = 0; q < G; ++q) acc[q] = sh;
+        const float *wp = a.w + ((int64_t)(ab * a.nb2 + nb) * nkb * 64 + lane) * 4;
+        if (NKB) {
+#pragma unroll
+          for (int kb = 0; kb < (NKB ? NKB : 1); ++kb) {
+            const f32x4 wf = *reinterpret_cast<const f32x4 *>(wp + (int64_t)kb * 256);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int q = 0; q < G; ++q) acc[q] = mfma4(wf[j], bf[q][kb][j], acc[q]);
+          }
+        } else {
+          for (int kb = 0; kb < nkb; ++kb) {
+            const f32x4 wf = *reinterpret_cast<const f32x4 *>(wp + (int64_t)kb * 256);
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+              const f32x4 xq = load_in_quad(a.in, m[q], a.cin, 16 * kb + 4 * g);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) acc[q] = mfma4(wf[j], xq[j], acc[q]);
+            }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < G; ++q)
+          if (ok[q]) store_quad(a.out + obase[q] + aboff, 16 * nb + 4 * g, N2, acc[q], a.act);
+      }
+    }
+  }
+}
+
+// a concatenation written out (a program that holds a Conv3DTranspose may feed one to a
+// 1x1x1 conv): each operand a cubic buffer seen through up / crop
+__global__ void concat_view_f32(const float *__restrict__ a, int aD, int aC, int aup, int acrop,
+                                const float *__restrict__ b, int bD, int bC, int bup, int bcrop,
+                                float *__restrict__ out, int64_t n_out, int od) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  const int C = aC + bC;
+  int64_t t = i;
+  const int c = (int)(t % C); t /= C;
+  const int x = (int)(t % od); t /= od;
+  const int y = (int)(t % od); t /= od;
+  const int z = (int)(t % od); t /= od;
+  if (c < aC)
+    out[i] = a[((((t * aD + (z + acrop) / aup) * aD + (y + acrop) / aup) * (int64_t)aD + (x + acrop) / aup) * aC) + c];
+  else
+    out[i] = b[((((t * bD + (z + bcrop) / bup) * bD + (y + bcrop) / bup) * (int64_t)bD + (x + bcrop) / bup) * bC) + c - aC];
+}
+
 // out = act(a + b), either operand seen through a centre crop of a larger cubic tile
 // (resnet_like's shortcuts, flypylib/fplmodels.py:174-208); channels-last, C % 4 == 0 not
 // required
@@ -949,6 +1079,45 @@ void pack_conv1_f32(const float *W, const float *scale, int cin, int cout, int m
       }
 }
 
+// deconv fragments [ab][nb][kb][lane][j] = W[tap = 2 ab + c'][co][16 kb + 4g + j] * scale[co]
+// with N = 16 nb + (lane & 15) = c' * cout + co inside the (a, b) row, then the shifts by N
+void pack_deconv_f32(const float *W, const float *scale, const float *shift, int cin, int cout,
+                     std::vector<float> *out) {
+  const int nkb = (cin + 15) / 16, nb2 = (2 * cout + 15) / 16;
+  out->assign((size_t)4 * nb2 * nkb * 256 + (size_t)16 * nb2, 0.f);
+  for (int ab = 0; ab < 4; ++ab)
+    for (int nb = 0; nb < nb2; ++nb)
+      for (int kb = 0; kb < nkb; ++kb)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int n = 16 * nb + (lane & 15), g = lane >> 4;
+          if (n >= 2 * cout) continue;
+          const int tap = 2 * ab + n / cout, co = n % cout;
+          for (int j = 0; j < 4; ++j) {
+            const int ci = 16 * kb + 4 * g + j;
+            if (ci >= cin) continue;
+            (*out)[((((size_t)ab * nb2 + nb) * nkb + kb) * 64 + lane) * 4 + j] =
+                W[((size_t)tap * cout + co) * cin + ci] * scale[co];
+          }
+        }
+  float *sh = out->data() + (size_t)4 * nb2 * nkb * 256;
+  for (int n = 0; n < 2 * cout; ++n) sh[n] = shift[n % cout];
+}
+
+int launch_deconv(fpl_ctx *ctx, DeconvF &a) {
+  const int nkb = (a.cin + 15) / 16;
+  const int G = nkb <= 2 ? 4 : 2;          // as instantiated below
+  const int64_t groups = ceil_div64(a.M, 16 * G);
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div64(groups, 4), (int64_t)ctx->n_cu * 8);
+  TimedLaunch tl(ctx, "mfma_deconv2_f32");
+  switch (nkb) {
+    case 1: deconv2_f32<1, 4><<<grid, 256, 0, ctx->stream>>>(a); break;
+    case 2: deconv2_f32<2, 4><<<grid, 256, 0, ctx->stream>>>(a); break;
+    case 3: deconv2_f32<3, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
+    default: deconv2_f32<0, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
+  }
+  return 0;
+}
+
 // stem fragments [q][mb][lane][j] = W[tap = 16q + 4g + j][0][16mb + (lane&15)] * scale
 void pack_stem_f32(const float *W, const float *scale, int cout, int mb, std::vector<float> *out) {
   out->assign((size_t)2 * mb * 256, 0.f);
@@ -991,6 +1160,7 @@ void f32_state_free(fpl_ctx *, void *p) {
 struct View {
   const float *p = nullptr;
   int D = 0, C = 0;              // real buffer dims (cubic tiles) and channels
+  int H = 0, W = 0;              // = D but in a program of voxel GEMMs only (fpl_mfma_f32_any_dims)
   int up = 1, crop = 0;
   int dim = 0;                   // logical (viewed) edge
 };
@@ -1073,18 +1243,54 @@ int launch1(fpl_ctx *ctx, Conv1F &a) {
 
 }  // namespace
 
+// A concatenation stays virtual (two views, resolved by the conv3 that loads it) in every
+// program of the kinds the executor has always run.  In a program that holds a
+// Conv3DTranspose - new ground - one whose readers are not all multi-channel conv3s is
+// written out instead, so that a 1x1x1 conv may read it.  One pass per program: per op,
+// 1 = a concatenation that is written out.
+static std::vector<char> concats_written(const fpl_program *prog) {
+  std::vector<char> other_reader(prog->n_tensors, 0), out(prog->ops.size(), 0);
+  bool deconv = false;
+  other_reader[prog->out_tensor] = 1;
+  for (auto &op : prog->ops) {
+    deconv |= op.kind == FPL_OP_DECONV;
+    if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1) continue;
+    other_reader[op.src0] = 1;
+    if (op.src1 >= 0) other_reader[op.src1] = 1;
+  }
+  if (deconv)
+    for (size_t i = 0; i < prog->ops.size(); ++i)
+      out[i] = prog->ops[i].kind == FPL_OP_CONCAT && other_reader[prog->ops[i].dst];
+  return out;
+}
+
+// programs made of voxel GEMMs only (1x1x1 convs and Conv3DTransposes) run on tiles of any
+// extents; everything else is written for cubic tiles
+bool fpl_mfma_f32_any_dims(const fpl_program *prog) {
+  for (auto &op : prog->ops)
+    if (!(op.kind == FPL_OP_DECONV || (op.kind == FPL_OP_CONV && op.k == 1))) return false;
+  return true;
+}
+
 // every op kind; conv3 needs cout <= 64 and <= 12 channel chunks
 bool fpl_mfma_f32_supported(const fpl_program *prog) {
   // tensors that exist only as an index remap (up / crop / concat): consumable by a
   // multi-channel conv3 (its tile loader applies the remap), nothing else
-  std::vector<char> is_view(prog->n_tensors, 0);
-  for (auto &op : prog->ops) {
+  std::vector<char> is_view(prog->n_tensors, 0);       // 1: up / crop view, 2: virtual concatenation
+  const std::vector<char> written = concats_written(prog);
+  for (size_t i = 0; i < prog->ops.size(); ++i) {
+    const fpl_op &op = prog->ops[i];
     const bool v0 = is_view[op.src0], v1 = op.src1 >= 0 && is_view[op.src1];
     if (op.kind == FPL_OP_UP || op.kind == FPL_OP_CROP) {
       if (v0) return false;
       is_view[op.dst] = 1;
     } else if (op.kind == FPL_OP_CONCAT) {
-      is_view[op.dst] = 1;
+      if (written[i]) {
+        // operands: buffers or up / crop views of buffers, not a virtual concatenation
+        if (is_view[op.src0] == 2 || is_view[op.src1] == 2) return false;
+      } else {
+        is_view[op.dst] = 2;
+      }
     } else if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1) {
       if (v1) return false;
     } else if (op.kind == FPL_OP_ADD) {
@@ -1105,6 +1311,7 @@ bool fpl_mfma_f32_supported(const fpl_program *prog) {
       if (op.k == 3 && (op.cout > 256 || op.cin > 12 * 16)) return false;
       if (op.k == 1 && op.cout > 128) return false;
     }
+    if (op.kind == FPL_OP_DECONV && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
   }
   return true;
 }
@@ -1112,7 +1319,17 @@ bool fpl_mfma_f32_supported(const fpl_program *prog) {
 // in: (n, T,T,T) f32 on the device (cubic tiles); out: (n, d,d,d, c) f32
 int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T,
                          float *out) {
+  const int32_t dims[3] = {T, T, T};
+  return fpl_forward_mfma_f32_dims(ctx, prog, in, n, dims, out);
+}
+
+// ... or (n, dims) tiles of any extents for a program of voxel GEMMs (fpl_mfma_f32_any_dims)
+int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, int n,
+                              const int32_t dims[3], float *out) {
   FPL_REQUIRE(ctx, fpl_mfma_f32_supported(prog), "program has ops the fp32 MFMA executor lacks");
+  const int T = dims[0];
+  FPL_REQUIRE(ctx, (dims[0] == dims[1] && dims[1] == dims[2]) || fpl_mfma_f32_any_dims(prog),
+              "the fp32 MFMA executor runs this program on cubic tiles only");
   F32State *st = (F32State *)prog->fast_state_f32;
   if (!st) {
     st = new F32State();
@@ -1125,6 +1342,13 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
     st->off.assign(prog->ops.size(), 0);
     for (size_t i = 0; i < prog->ops.size(); ++i) {
       const fpl_op &op = prog->ops[i];
+      if (op.kind == FPL_OP_DECONV) {
+        std::vector<float> f;
+        pack_deconv_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
+        st->off[i] = all.size();
+        all.insert(all.end(), f.begin(), f.end());
+        continue;
+      }
       if (op.kind != FPL_OP_CONV) continue;
       std::vector<float> f;
       const int mb = (op.cout + 15) / 16;
@@ -1149,8 +1373,9 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
     st->version = prog->arena_version;
   }
   DevTemp tmp(ctx);
+  const std::vector<char> written = concats_written(prog);
   std::vector<View> view(prog->n_tensors);
-  view[0].p = in; view[0].D = T; view[0].C = 1; view[0].dim = T;
+  view[0].p = in; view[0].D = T; view[0].H = dims[1]; view[0].W = dims[2]; view[0].C = 1; view[0].dim = T;
   hipStream_t stm = ctx->stream;
   auto cube = [](int d) { return (int64_t)d * d * d; };
   for (size_t i = 0; i < prog->ops.size(); ++i) {
@@ -1174,6 +1399,26 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
         const View b = view[op.src1];
         FPL_REQUIRE(ctx, a.dim == b.dim, "op %zu: concatenate of %d^3 with %d^3 - input size is "
                     "not compatible with this architecture", i, a.dim, b.dim);
+        if (written[i]) {
+          FPL_REQUIRE(ctx, a.p && b.p, "op %zu: concatenate of a concatenation", i);
+          const int64_t no = (int64_t)n * cube(a.dim) * (a.C + b.C);
+          float *cdst = out;
+          if (op.dst != prog->out_tensor) {
+            void *q;
+            FPL_TRY(tmp.alloc((size_t)no * sizeof(float) + 64, &q));
+            cdst = (float *)q;
+          }
+          {
+            TimedLaunch tl(ctx, "mfma_concat_f32");
+            concat_view_f32<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(
+                a.p, a.D, a.C, a.up, a.crop, b.p, b.D, b.C, b.up, b.crop, cdst, no, a.dim);
+          }
+          FPL_HIP(ctx, hipGetLastError());
+          o = View();
+          o.p = cdst; o.D = o.H = o.W = o.dim = a.dim; o.C = a.C + b.C;
+          view[op.dst] = o;
+          continue;
+        }
         o = a; o.p = nullptr; o.dim = a.dim; o.C = a.C + b.C;
         view[op.dst] = o;
         continue;
@@ -1213,20 +1458,34 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
     if (op.kind == FPL_OP_CONV) { od = a.dim - (op.k - 1); oc = op.cout; }
     if (op.kind == FPL_OP_POOL) { od = a.dim / 2; oc = a.C; }
     if (op.kind == FPL_OP_ADD) { od = a.dim; oc = a.C; }
+    if (op.kind == FPL_OP_DECONV) { od = 2 * a.dim; oc = op.cout; }
     FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
     const int od_conv = od;                       // conv3's own output edge
     const fpl_op &last = fusep >= 0 ? prog->ops[fusep] : (fuse1 >= 0 ? prog->ops[fuse1] : op);
     if (fuse1 >= 0) { oc = prog->ops[fuse1].cout; if (fusep >= 0) od = od / 2; }
     FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
+    // extents of the result: cubic, but for the voxel GEMMs, which follow their input's
+    int oD = od, oH = od, oW = od;
+    if (op.kind == FPL_OP_DECONV) { oD = 2 * a.D; oH = 2 * a.H; oW = 2 * a.W; }
+    else if (op.kind == FPL_OP_CONV && op.k == 1) { oD = a.D; oH = a.H; oW = a.W; }
     if (last.dst == prog->out_tensor) {
       dst = out;
     } else {
       void *q;
-      FPL_TRY(tmp.alloc((size_t)n * cube(od) * oc * sizeof(float) + 64, &q));
+      FPL_TRY(tmp.alloc((size_t)n * oD * oH * oW * oc * sizeof(float) + 64, &q));
       dst = (float *)q;
     }
-    o.p = dst; o.D = od; o.C = oc; o.dim = od;
-    if (op.kind == FPL_OP_ADD) {
+    o.p = dst; o.D = oD; o.H = oH; o.W = oW; o.C = oc; o.dim = od;
+    if (op.kind == FPL_OP_DECONV) {
+      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: Conv3DTranspose of a view", i);
+      DeconvF c;
+      c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
+      c.nb2 = (2 * op.cout + 15) / 16;
+      c.w = st->frags + st->off[i];
+      c.shift = c.w + (size_t)4 * c.nb2 * ((op.cin + 15) / 16) * 256;
+      c.act = op.act; c.out = dst; c.cout = op.cout;
+      FPL_TRY(launch_deconv(ctx, c));
+    } else if (op.kind == FPL_OP_ADD) {
       const View b = view[op.src1];
       FPL_REQUIRE(ctx, a.p && b.p && a.up == 1 && b.up == 1 && a.dim == b.dim && a.C == b.C,
                   "op %zu: add of incompatible tensors", i);
@@ -1242,7 +1501,7 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
     } else if (op.k == 1) {
       FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0, "op %zu: conv1 of a view", i);
       Conv1F c;
-      c.in = a.p; c.M = (int64_t)n * cube(a.D); c.cin = op.cin;
+      c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin;
       c.w = st->frags + st->off[i]; c.shift = prog->arena_dev + op.shift_off; c.act = op.act;
       c.out = dst; c.cout = op.cout; c.stats = nullptr;
       const int mb = (op.cout + 15) / 16;

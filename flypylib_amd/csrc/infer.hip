@@ -94,13 +94,21 @@ __global__ void upsample_out(const float *__restrict__ in, float *__restrict__ o
   out[i] = in[(((t * d + z / s0) * h + y / s1) * (int64_t)w + x / s2) * c + cc];
 }
 
+bool has_deconv(const fpl_program *prog) {
+  for (auto &op : prog->ops)
+    if (op.kind == FPL_OP_DECONV) return true;
+  return false;
+}
+
 // may neighbouring tiles of the reference lattice be computed as one larger tile with the
 // same results?  (no upsampling: then the output's stride is the deepest pooling level;
 // every pool sees even extents; the lattice pitch is a multiple of the stride)
 bool tiles_mergeable(const fpl_program *prog, const std::vector<TensorShape> &shp,
                      const int32_t out_sz[3]) {
   for (auto &op : prog->ops) {
-    if (op.kind == FPL_OP_UP) return false;
+    // (a Conv3DTranspose returns to a finer lattice than the deepest pool's, which the argument
+    // below does not cover: declined like an upsampling - DESIGN.md, "Conv3DTranspose")
+    if (op.kind == FPL_OP_UP || op.kind == FPL_OP_DECONV) return false;
     if (op.kind == FPL_OP_POOL) {
       const TensorShape &t = shp[op.src0];
       if (t.d % op.p[0] || t.h % op.p[1] || t.w % op.p[2]) return false;
@@ -160,9 +168,11 @@ int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
     net_out = (float *)p;
   }
   const bool cubic = in_dims[0] == in_dims[1] && in_dims[1] == in_dims[2];
-  if (cubic && fpl_mfma_f32_supported(prog) && !getenv("FPL_FORCE_PEROP")) {
+  // (a program that holds a Conv3DTranspose and nothing but voxel GEMMs runs on any extents)
+  const bool any_dims = has_deconv(prog) && fpl_mfma_f32_any_dims(prog);
+  if ((cubic || any_dims) && fpl_mfma_f32_supported(prog) && !getenv("FPL_FORCE_PEROP")) {
     set_last_path(ctx, "mfma_f32");
-    FPL_TRY(fpl_forward_mfma_f32(ctx, prog, in_dev, n, in_dims[0], net_out));
+    FPL_TRY(fpl_forward_mfma_f32_dims(ctx, prog, in_dev, n, in_dims, net_out));
   } else {
     set_last_path(ctx, "perop_f32");
     FPL_TRY(fpl_forward_generic(ctx, prog, in_dev, n, in_dims, net_out));
@@ -245,6 +255,9 @@ static int infer_volume_impl(fpl_ctx *ctx, fpl_program *prog, const void *src,
     dst_dev = (float *)p;
     dst_base = wr_lo;
   }
+  FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_deconv(prog),
+              "fpl_infer_volume: no 16-bit MFMA kernels for the layer Conv3DTranspose: this network runs in "
+              "fp32 only; use precision f32 (or 'auto')");
   // the fused fast path writes every valid voxel itself: only the border shell
   // needs clearing there; the per-op path stitches tiles into a zeroed volume
   const bool cubic = tile_in[0] == tile_in[1] && tile_in[1] == tile_in[2];
@@ -639,8 +652,9 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
     int32_t out_sz[3];
     for (int a = 0; a < 3; ++a) out_sz[a] = tile_in[a] - 2 * offset[a];
     const bool cubic = tile_in[0] == tile_in[1] && tile_in[1] == tile_in[2];
-    const bool have_split = fpl_split_path_available(prog, FPL_PREC_F16S, offset, out_sz) ||
-                            (cubic && fpl_unet_fast_available_f16s(prog, FPL_PREC_F16S));
+    const bool have_split = !has_deconv(prog) &&
+                            (fpl_split_path_available(prog, FPL_PREC_F16S, offset, out_sz) ||
+                             (cubic && fpl_unet_fast_available_f16s(prog, FPL_PREC_F16S)));
     if (have_split && prog->half_range_bad_version != prog->arena_version) {
       const int rc = run(FPL_PREC_F16S, &bits);
       if (rc == 0 && !bits) return 0;

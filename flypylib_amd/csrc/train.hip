@@ -804,6 +804,126 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(
     }
 }
 
+// ---- Conv3DTranspose(cout, 2, strides 2) backward (FPL_L_DECONV; the forward is
+// deconv2_direct_f32, conv_direct.h).  x (n, D, H, W, cin), w [8][cout][cin],
+// dy (n, 2D, 2H, 2W, cout).  No float atomics anywhere: every sum has a fixed order, so
+// equal inputs give equal bits.
+// first output element of input voxel m's 2x2x2 block, tap (a, b, c)
+__device__ __forceinline__ int64_t deconv_out_row(int64_t m, int tap, int D, int H, int W) {
+  int64_t t = m;
+  const int x = (int)(t % W); t /= W;
+  const int y = (int)(t % H); t /= H;
+  const int z = (int)(t % D); t /= D;
+  return ((t * (2 * D) + 2 * z + (tap >> 2)) * (2 * H) + 2 * y + ((tap >> 1) & 1)) * (int64_t)(2 * W) +
+         2 * x + (tap & 1);
+}
+
+// input gradient: dy gathered by parity, times the transposed weights:
+// dx[m][ci] (+)= sum_tap sum_co dy[row(m, tap)][co] * w[tap][co][ci]; one thread per element
+template <bool ACC>
+__global__ __launch_bounds__(256) void deconv2_dgrad_f32(
+    const float *__restrict__ dy, const float *__restrict__ w, float *__restrict__ dx,
+    int64_t n_in, int D, int H, int W, int cin, int cout) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_in) return;
+  const int ci = (int)(i % cin);
+  const int64_t m = i / cin;
+  float acc = 0.f;
+  for (int tap = 0; tap < 8; ++tap) {
+    const float *gp = dy + deconv_out_row(m, tap, D, H, W) * cout;
+    const float *wp = w + (int64_t)tap * cout * cin + ci;
+    for (int co = 0; co < cout; ++co) acc = fmaf(gp[co], wp[(int64_t)co * cin], acc);
+  }
+  dx[i] = ACC ? dx[i] + acc : acc;
+}
+
+// weight gradient, stage 1: workgroup (chunk, tap) sums dy[row(m, tap)][co] * x[m][ci] over its
+// chunk of input voxels, DC_VS voxels at a time through LDS, each thread its own (co, ci)
+// pair in voxel order, into part[chunk][tap][co][ci]
+constexpr int DC_VS = 16;
+__global__ __launch_bounds__(256) void deconv2_wgrad_partial_f32(
+    const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ part,
+    int64_t M, int64_t chunk, int D, int H, int W, int cin, int cout) {
+  extern __shared__ float dc_sh[];                 // xs[DC_VS][cin], gs[DC_VS][cout]
+  float *xs = dc_sh, *gs = dc_sh + DC_VS * cin;
+  const int tap = blockIdx.y;
+  const int64_t m0 = (int64_t)blockIdx.x * chunk;
+  const int64_t m1 = m0 + chunk < M ? m0 + chunk : M;
+  const int npair = cin * cout;
+  float *out = part + ((int64_t)blockIdx.x * 8 + tap) * npair;
+  for (int p0 = 0; p0 < npair; p0 += 256) {        // one (co, ci) pair per thread and pass
+    const int pr = p0 + threadIdx.x;
+    const int co = pr < npair ? pr / cin : 0, ci = pr < npair ? pr % cin : 0;
+    float acc = 0.f;
+    for (int64_t mb = m0; mb < m1; mb += DC_VS) {
+      __syncthreads();
+      for (int e = threadIdx.x; e < DC_VS * cin; e += 256) {
+        const int64_t m = mb + e / cin;
+        xs[e] = m < m1 ? x[m * cin + e % cin] : 0.f;
+      }
+      for (int e = threadIdx.x; e < DC_VS * cout; e += 256) {
+        const int64_t m = mb + e / cout;
+        gs[e] = m < m1 ? dy[deconv_out_row(m, tap, D, H, W) * cout + e % cout] : 0.f;
+      }
+      __syncthreads();
+      for (int v = 0; v < DC_VS; ++v) acc = fmaf(gs[v * cout + co], xs[v * cin + ci], acc);
+    }
+    if (pr < npair) out[pr] = acc;
+  }
+}
+// stage 2: dw[i] += the partials of element i in chunk order
+__global__ void deconv2_wgrad_sum_f32(const float *__restrict__ part, int nchunk, int64_t n,
+                                      float *__restrict__ dw) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+  for (int k = 0; k < nchunk; ++k) s += part[(int64_t)k * n + i];
+  dw[i] += s;
+}
+
+// Weight gradient of a valid convolution with sums in a fixed order, for a network that holds a
+// Conv3DTranspose (fpl_trainer_step, `fixed_order`): the same two stages as above.  Workgroup
+// (chunk of output voxels, tap): part[chunk][tap][ci][co] = sum_m x[m + tap][ci] * dy[m][co].
+__global__ __launch_bounds__(256) void conv_wgrad_partial_f32(
+    const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ part,
+    int64_t M, int64_t chunk, int D, int H, int W, int cin, int od, int oh, int ow, int cout, int k) {
+  extern __shared__ float dc_sh[];                 // xs[DC_VS][cin], gs[DC_VS][cout]
+  float *xs = dc_sh, *gs = dc_sh + DC_VS * cin;
+  const int tap = blockIdx.y;
+  const int dz = tap / (k * k), dyy = (tap / k) % k, dxx = tap % k;
+  const int64_t m0 = (int64_t)blockIdx.x * chunk;
+  const int64_t m1 = m0 + chunk < M ? m0 + chunk : M;
+  const int npair = cin * cout;
+  float *out = part + ((int64_t)blockIdx.x * gridDim.y + tap) * npair;
+  for (int p0 = 0; p0 < npair; p0 += 256) {        // one (ci, co) pair per thread and pass
+    const int pr = p0 + threadIdx.x;
+    const int ci = pr < npair ? pr / cout : 0, co = pr < npair ? pr % cout : 0;
+    float acc = 0.f;
+    for (int64_t mb = m0; mb < m1; mb += DC_VS) {
+      __syncthreads();
+      for (int e = threadIdx.x; e < DC_VS * cin; e += 256) {
+        const int64_t m = mb + e / cin;
+        float v = 0.f;
+        if (m < m1) {
+          int64_t t = m;
+          const int ox = (int)(t % ow); t /= ow;
+          const int oy = (int)(t % oh); t /= oh;
+          const int oz = (int)(t % od); t /= od;
+          v = x[((((t * D + oz + dz) * H + oy + dyy) * (int64_t)W + ox + dxx) * cin) + e % cin];
+        }
+        xs[e] = v;
+      }
+      for (int e = threadIdx.x; e < DC_VS * cout; e += 256) {
+        const int64_t m = mb + e / cout;
+        gs[e] = m < m1 ? dy[m * cout + e % cout] : 0.f;
+      }
+      __syncthreads();
+      for (int v = 0; v < DC_VS; ++v) acc = fmaf(xs[v * cin + ci], gs[v * cout + co], acc);
+    }
+    if (pr < npair) out[pr] = acc;
+  }
+}
+
 __global__ void adam_update(float *__restrict__ w, const float *__restrict__ g,
                             float *__restrict__ m, float *__restrict__ v,
                             const uint8_t *__restrict__ kind, int64_t n,
@@ -859,6 +979,10 @@ int shapes_for(fpl_ctx *ctx, const fpl_trainer *t, const int32_t patch[3],
       case FPL_L_CONV:
         FPL_REQUIRE(ctx, a.c == L.cin, "layer %zu: conv cin mismatch", i);
         o.d = a.d - L.k + 1; o.h = a.h - L.k + 1; o.w = a.w - L.k + 1; o.c = L.cout;
+        break;
+      case FPL_L_DECONV:
+        FPL_REQUIRE(ctx, a.c == L.cin, "layer %zu: Conv3DTranspose cin mismatch", i);
+        o.d = 2 * a.d; o.h = 2 * a.h; o.w = 2 * a.w; o.c = L.cout;
         break;
       case FPL_L_POOL:
         FPL_REQUIRE(ctx, L.p[0] == 2 && L.p[1] == 2 && L.p[2] == 2,
@@ -926,6 +1050,24 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
           FPL_REQUIRE(ctx, !(layers[j].kind == FPL_L_BN && layers[j].src0 == L.dst),
                       "layer %d: a conv with a relu activation feeding BatchNorm (layer %d) "
                       "is not trainable", i, j);
+    } else if (L.kind == FPL_L_DECONV) {
+      FPL_REQUIRE(ctx, L.k == 2 && L.p[0] == 2 && L.p[1] == 2 && L.p[2] == 2,
+                  "layer %d: Conv3DTranspose kernel %d strides (%d,%d,%d) (only kernel 2 with strides 2)",
+                  i, L.k, L.p[0], L.p[1], L.p[2]);
+      FPL_REQUIRE(ctx, L.cin > 0 && L.cout > 0 && L.cin <= 256 && L.cout <= 256,
+                  "layer %d: Conv3DTranspose %d -> %d channels (1 .. 256)", i, L.cin, L.cout);
+      const int64_t kk = (int64_t)8 * L.cin * L.cout;
+      FPL_REQUIRE(ctx, L.w_off[0] >= 0 && L.w_off[0] + kk <= n_weights &&
+                           (!L.use_bias || (L.w_off[1] >= 0 && L.w_off[1] + L.cout <= n_weights)),
+                  "layer %d: weight offsets exceed the arena", i);
+      FPL_REQUIRE(ctx, L.act == FPL_ACT_NONE || L.act == FPL_ACT_RELU,
+                  "layer %d: Conv3DTranspose activation %d (none or relu)", i, L.act);
+      FPL_REQUIRE(ctx, L.dst != out_tensor, "layer %d: the head must be a sigmoid conv", i);
+      if (L.act == FPL_ACT_RELU)
+        for (int j = 0; j < n_layers; ++j)
+          FPL_REQUIRE(ctx, !(layers[j].kind == FPL_L_BN && layers[j].src0 == L.dst),
+                      "layer %d: a Conv3DTranspose with a relu activation feeding BatchNorm "
+                      "(layer %d) is not trainable", i, j);
     } else if (L.kind == FPL_L_BN) {
       FPL_REQUIRE(ctx, L.cin <= 256, "layer %d: > 256 channels", i);
       for (int q = 0; q < 4; ++q)
@@ -1085,6 +1227,13 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   const char *direct_env = getenv("FPL_TRAIN_DIRECT");
   const int direct_mask = direct_env ? ((atoi(direct_env) & 3) ? (atoi(direct_env) & 3) : 3) : 0;
   const bool use_mfma = !(direct_mask & 1), use_mfma_bwd = !(direct_mask & 2);
+  // A network that holds a Conv3DTranspose is new ground and trains with every weight gradient
+  // summed in a fixed order: its convolutions' weight gradients come from conv_wgrad_partial_f32
+  // (the fp32 MFMA weight-gradient kernels and conv_wgrad_f32 add their sums with float atomics),
+  // and the passes that leave a gradient tensor to those kernels' loaders are not fused.  The
+  // networks without the layer run exactly what they ran before.
+  bool fixed_order = false;
+  for (const fpl_layer &L : t->layers) fixed_order |= L.kind == FPL_L_DECONV;
   std::vector<TShape> shp;
   FPL_TRY(shapes_for(ctx, t, patch, &shp));
   const int nt = t->n_tensors;
@@ -1125,7 +1274,11 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   }
   FPL_HIP(ctx, hipMemsetAsync(t->g, 0, (size_t)t->n_w * 4, st));
   void *partv;
-  const int64_t max_rows = (int64_t)batch * shp[0].vox();
+  // (rows of the largest tensor: the input's, unless a Conv3DTranspose grows past it)
+  int64_t max_rows = (int64_t)batch * shp[0].vox();
+  for (int li = 0; li < nl; ++li)
+    if (t->layers[li].kind == FPL_L_DECONV)
+      max_rows = std::max(max_rows, (int64_t)batch * shp[t->layers[li].dst].vox());
   const int max_nb = (int)std::max<int64_t>(ceil_div64(max_rows, 4096), 2048) + 1;
   FPL_TRY(tmp.alloc((size_t)max_nb * 2 * 256 * sizeof(double), &partv));
   double *part = (double *)partv;
@@ -1177,7 +1330,7 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   // input-gradient loaders form it from the pooled gradient (FplPoolGrad)
   std::vector<FplPoolGrad> pool_grad(nt, FplPoolGrad{});
   for (int li = 0; li + 2 < nl; ++li) {
-    if (!bn_fused[li] || pool_fused[li] || !use_mfma || !use_mfma_bwd) continue;
+    if (!bn_fused[li] || pool_fused[li] || !use_mfma || !use_mfma_bwd || fixed_order) continue;
     const fpl_layer &B = t->layers[li], &R = t->layers[li + 1];
     const bool v4 = shp[B.src0].c % 4 == 0 && B.w_off[0] % 4 == 0 && B.w_off[1] % 4 == 0;
     if (!v4 || n_cons[R.dst] != 1 || R.dst == t->out_tensor) continue;
@@ -1258,6 +1411,13 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
           TimedLaunch tl(ctx, "train_elementwise");
           relu_fwd<<<g1(n), 256, 0, st>>>(pre[L.dst], val[L.dst], n);
         }
+        break;
+      }
+      case FPL_L_DECONV: {
+        const float *bias = L.use_bias ? t->w + L.w_off[1] : t->zeros;
+        TimedLaunch tl(ctx, "train_deconv_fwd");
+        deconv2_direct_f32<<<g1(n), 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
+            val[L.dst], n, a.d, a.h, a.w, a.c, o.c, L.act);
         break;
       }
       case FPL_L_BN: {
@@ -1394,6 +1554,7 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
     if (L.kind == FPL_L_POOL && pool_tiles(shp[ti])) assign[ti] = 1;
     if (L.kind == FPL_L_CONV && use_mfma_bwd && fpl_tm_bwd_supported(L.k, L.cin, L.cout))
       assign[ti] = 1;
+    if (L.kind == FPL_L_DECONV) assign[ti] = 1;
   }
   for (int ti = 1; ti < nt; ++ti) {
     if (!val[ti]) continue;
@@ -1421,6 +1582,25 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   }
 
   // ------------------------------ backward -----------------------------------
+  // a convolution's weight gradient as per-workgroup partials added in chunk order (fixed_order)
+  auto wgrad_fixed_order = [&](const fpl_layer &L, const TShape &a, const TShape &o, const float *dy) -> int {
+    const int64_t M = (int64_t)batch * o.vox();
+    const int taps = L.k * L.k * L.k;
+    const int64_t per = (int64_t)taps * L.cin * L.cout;
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)64 << 20) / (per * 4)));
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div64(M, 256)));
+    const int64_t chunk = ceil_div64(ceil_div64(M, nchunk), DC_VS) * DC_VS;
+    const int64_t nch = ceil_div64(M, chunk);
+    float *pw;
+    FPL_TRY(alloc_f(nch * per, &pw));
+    TimedLaunch tl(ctx, "train_conv_wgrad_fixed");
+    conv_wgrad_partial_f32<<<dim3((unsigned)nch, (unsigned)taps), 256,
+                             (size_t)DC_VS * (L.cin + L.cout) * sizeof(float), st>>>(
+        val[L.src0], dy, pw, M, chunk, a.d, a.h, a.w, L.cin, o.d, o.h, o.w, L.cout, L.k);
+    deconv2_wgrad_sum_f32<<<g1(per), 256, 0, st>>>(pw, (int)nch, per, t->g + L.w_off[0]);
+    tmp.release(pw);
+    return 0;
+  };
   for (int li = nl - 1; li >= 0; --li) {
     const fpl_layer &L = t->layers[li];
     const TShape a = shp[L.src0], o = shp[L.dst];
@@ -1465,6 +1645,8 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
           const float *xin = viewed ? view_of(L.src0, &bv) : val[L.src0];
           const FplBnGrad *bgv = bn_grad[L.dst].g ? &bn_grad[L.dst] : nullptr;
           const FplPoolGrad *pgv = pool_grad[L.dst].x ? &pool_grad[L.dst] : nullptr;
+          if (fixed_order) FPL_TRY(wgrad_fixed_order(L, a, o, dy));   // (no view, no fused gradient: see above)
+          else
           FPL_TRY(fpl_tm_conv_wgrad(ctx, xin, batch, a.d, a.h, a.w, a.c, dy, L.k,
                                     L.cout, t->g + L.w_off[0], viewed ? &bv : nullptr, bgv, pgv));
           if (L.use_bias) {
@@ -1504,7 +1686,9 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
           }
           break;
         }
-        {
+        if (fixed_order) {
+          FPL_TRY(wgrad_fixed_order(L, a, o, dy));
+        } else {
           const int cit = (L.cin + 47) / 48, cot = (L.cout + 47) / 48;
           dim3 g((unsigned)(taps * cit * cot), (unsigned)ceil_div64(n_vox, WG_CHUNK));
           TimedLaunch tl(ctx, "train_conv_wgrad");
@@ -1532,6 +1716,57 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
             conv_dgrad_f32<1><<<g, 256, 0, st>>>(dy, t->w + L.w_off[0], dx, in_vox, a.d, a.h,
                 a.w, a.c, o.d, o.h, o.w, o.c, L.k);
           }
+        }
+        break;
+      }
+      case FPL_L_DECONV: {
+        const int64_t n_vox = (int64_t)batch * o.vox();        // output voxels: dy's rows
+        const int64_t M = (int64_t)batch * a.vox();            // input voxels
+        if (L.act == FPL_ACT_RELU) {
+          // as for a conv: the gradient of the pre-activation in place, dy *= (y > 0), before
+          // anything below reads dy
+          const int64_t n4 = n / 4;
+          TimedLaunch tl(ctx, "train_elementwise");
+          if (n4 > 0) {
+            const unsigned gr = (unsigned)std::min<int64_t>(ceil_div64(n4, 256), (int64_t)ctx->n_cu * 8);
+            relu_mask_grad<<<gr, 256, 0, st>>>((const float4 *)val[L.dst], (float4 *)dy, n4);
+          }
+          if (n % 4) relu_mask_grad_tail<<<1, 64, 0, st>>>(val[L.dst], dy, 4 * n4, n);
+        }
+        {
+          // per-workgroup partials summed in chunk order; chunks of >= 256 voxels, as many as
+          // a 64 MB partial buffer allows, at most 256
+          const int64_t per = (int64_t)8 * L.cin * L.cout;
+          const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)64 << 20) / (per * 4)));
+          const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div64(M, 256)));
+          const int64_t chunk = ceil_div64(ceil_div64(M, nchunk), DC_VS) * DC_VS;
+          const int64_t nch = ceil_div64(M, chunk);
+          float *pw;
+          FPL_TRY(alloc_f(nch * per, &pw));
+          TimedLaunch tl(ctx, "train_deconv_wgrad");
+          deconv2_wgrad_partial_f32<<<dim3((unsigned)nch, 8), 256,
+                                      (size_t)DC_VS * (L.cin + L.cout) * sizeof(float), st>>>(
+              val[L.src0], dy, pw, M, chunk, a.d, a.h, a.w, L.cin, L.cout);
+          deconv2_wgrad_sum_f32<<<g1(per), 256, 0, st>>>(pw, (int)nch, per, t->g + L.w_off[0]);
+          tmp.release(pw);
+        }
+        if (L.use_bias) {
+          const int rr = red_rows(n_vox), nb = (int)ceil_div64(n_vox, rr);
+          const int R = std::max(1, 256 / L.cout);
+          TimedLaunch tl(ctx, "train_bias_grad");
+          chan_reduce_partial<2><<<nb, dim3(L.cout, R), (size_t)L.cout * R * 2 * sizeof(double), st>>>(
+              dy, nullptr, nullptr, nullptr, n_vox, L.cout, rr, part);
+          finish_sums<<<L.cout, 256, 0, st>>>(part, nb, L.cout, t->g + L.w_off[1], nullptr, 1.f);
+        }
+        if (dx) {
+          const int64_t n_in = M * L.cin;
+          TimedLaunch tl(ctx, "train_deconv_dgrad");
+          if (assign[L.src0])
+            deconv2_dgrad_f32<false><<<g1(n_in), 256, 0, st>>>(dy, t->w + L.w_off[0], dx, n_in, a.d, a.h,
+                                                               a.w, L.cin, L.cout);
+          else
+            deconv2_dgrad_f32<true><<<g1(n_in), 256, 0, st>>>(dy, t->w + L.w_off[0], dx, n_in, a.d, a.h,
+                                                              a.w, L.cin, L.cout);
         }
         break;
       }
@@ -1571,7 +1806,7 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
             int prod = -1;
             for (int lp = 0; lp < li; ++lp)
               if (t->layers[lp].dst == L.src0) prod = lp;
-            if (dx && assign[L.src0] && prod >= 0 && t->layers[prod].kind == FPL_L_CONV &&
+            if (dx && assign[L.src0] && !fixed_order && prod >= 0 && t->layers[prod].kind == FPL_L_CONV &&
                 !t->layers[prod].use_bias && use_mfma_bwd && bn_view[t->layers[prod].src0] >= 0 &&
                 assign[t->layers[prod].src0] && grad[t->layers[prod].src0] &&
                 fpl_tm_bwd_supported(t->layers[prod].k, t->layers[prod].cin, t->layers[prod].cout) &&
@@ -1627,7 +1862,7 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
         int prod = -1;
         for (int lp = 0; lp < li; ++lp)
           if (t->layers[lp].dst == L.src0) prod = lp;
-        if (dx && v4 && bn_fused[li] && !acc && prod >= 0 && t->layers[prod].kind == FPL_L_CONV &&
+        if (dx && v4 && bn_fused[li] && !acc && !fixed_order && prod >= 0 && t->layers[prod].kind == FPL_L_CONV &&
             t->layers[prod].src0 == 0 && !t->layers[prod].use_bias && use_mfma_bwd &&
             fpl_tm_bwd_supported(t->layers[prod].k, t->layers[prod].cin, t->layers[prod].cout) &&
             fpl_tm_bn_grad_supported(t->layers[prod].k, t->layers[prod].cin, t->layers[prod].cout) &&

@@ -14,7 +14,10 @@ creation order per layer class (`conv3d_7` is the seventh Conv3D built in the se
 layers are classed by their weight names (kernel / bias -> convolution; gamma / beta /
 moving_mean / moving_variance -> batch normalisation), ordered by that number within the
 class (file order when a name has none) and assigned to the graph's convolution / BN
-nodes in creation order; every shape is checked.
+nodes in creation order; every shape is checked.  A Conv3DTranspose owns kernel / bias too
+(kernel `(2,2,2,Cout,Cin)`, out-channels first) and is numbered in a class of its own
+(`conv3d_transpose_1`): layers whose name says `transpose`, or - a user-named layer - whose
+kernel has the edge 2 no Conv3D of this package has, go to the graph's deconv nodes.
 
 Files are read with h5py when it is installed and with the package's own reader
 (`h5min`: the HDF5 subset Keras files use) otherwise; they are written with `h5min`.
@@ -93,17 +96,25 @@ def _creation_order(layers):
 def graph_weights_from_layers(graph, layers):
     """arrays in `graph.get_weights()` order"""
     convs = [(n, it) for n, it in layers if {r for r, _ in it} <= {'kernel', 'bias'}]
+    def is_transpose(layer):
+        # Keras' automatic name says so; a user-named layer is told by its kernel: (2,2,2,Cout,Cin)
+        # can only be a Conv3DTranspose here, the package's Conv3D kernels have edge 1 or 3
+        kern = [a for r, a in layer[1] if r == 'kernel']
+        return 'transpose' in layer[0].lower() or (len(kern) == 1 and tuple(kern[0].shape[:3]) == (2, 2, 2))
+    deconvs = [l for l in convs if is_transpose(l)]
+    convs = [l for l in convs if not is_transpose(l)]
     bns = [(n, it) for n, it in layers if {r for r, _ in it} & {'gamma', 'beta', 'moving_mean'}]
-    other = [n for n, it in layers if (n, it) not in convs and (n, it) not in bns]
+    other = [n for n, it in layers
+             if (n, it) not in convs and (n, it) not in bns and (n, it) not in deconvs]
     if other:
         raise ValueError('layers with weights this package has no counterpart for: %s' % other)
-    convs, bns = _creation_order(convs), _creation_order(bns)
+    convs, bns, deconvs = _creation_order(convs), _creation_order(bns), _creation_order(deconvs)
     out = [None] * len(graph.weights)
-    ci = bi = 0
+    ci = bi = di = 0
     for node in graph.nodes:
-        if node.kind not in ('conv', 'bn'):
+        if node.kind not in ('conv', 'bn', 'deconv'):
             continue
-        pool, idx = (convs, ci) if node.kind == 'conv' else (bns, bi)
+        pool, idx = {'conv': (convs, ci), 'bn': (bns, bi), 'deconv': (deconvs, di)}[node.kind]
         if idx >= len(pool):
             raise ValueError('the file has %d %s layers, the network needs more'
                              % (len(pool), node.kind))
@@ -120,11 +131,15 @@ def graph_weights_from_layers(graph, layers):
             out[slot] = np.asarray(arr, np.float32)
         if node.kind == 'conv':
             ci += 1
+        elif node.kind == 'deconv':
+            di += 1
         else:
             bi += 1
     if ci != len(convs) or bi != len(bns):
         raise ValueError('the file has %d conv / %d BN layers, the network %d / %d'
                          % (len(convs), len(bns), ci, bi))
+    if di != len(deconvs):
+        raise ValueError('the file has %d Conv3DTranspose layers, the network %d' % (len(deconvs), di))
     return out
 
 
@@ -133,7 +148,7 @@ def _trainable_slots(graph):
     (, bias) / gamma, beta - the moving statistics are not trainable"""
     out = []
     for node in graph.nodes:
-        if node.kind == 'conv':
+        if node.kind in ('conv', 'deconv'):
             out.extend(node.weight_slots)
         elif node.kind == 'bn':
             out.extend(node.weight_slots[:2])
@@ -208,8 +223,8 @@ def weight_tree(graph):
     """the `save_weights` tree of a graph (h5min.write's input): Keras' automatic layer
     names in creation order, one group per layer of the graph (weightless ones included,
     as Keras lists them)"""
-    roles = {'conv': ['kernel', 'bias'], 'bn': ['gamma', 'beta', 'moving_mean',
-                                                'moving_variance']}
+    roles = {'conv': ['kernel', 'bias'], 'deconv': ['kernel', 'bias'],
+             'bn': ['gamma', 'beta', 'moving_mean', 'moving_variance']}
     names = _layer_names(graph)
     layer_names, groups = [], {}
     for node in graph.nodes:
@@ -233,7 +248,8 @@ _KERAS_CLASS = {'conv': ('Conv3D', 'conv3d'), 'bn': ('BatchNormalization', 'batc
                 'relu': ('Activation', 'activation'), 'pool': ('MaxPooling3D', 'max_pooling3d'),
                 'drop': ('Dropout', 'dropout'), 'up': ('UpSampling3D', 'up_sampling3d'),
                 'crop': ('Cropping3D', 'cropping3d'), 'concat': ('Concatenate', 'concatenate'),
-                'add': ('Add', 'add'), 'input': ('InputLayer', 'input')}
+                'add': ('Add', 'add'), 'input': ('InputLayer', 'input'),
+                'deconv': ('Conv3DTranspose', 'conv3d_transpose')}
 
 
 def _layer_names(graph):
@@ -270,6 +286,15 @@ def model_config(graph):
             k = int(a['k'])
             cfg.update(filters=int(node.channels), kernel_size=[k, k, k], strides=[1, 1, 1],
                        padding='valid', data_format='channels_last', dilation_rate=[1, 1, 1],
+                       activation=a['activation'] or 'linear', use_bias=bool(a['use_bias']),
+                       kernel_initializer=glorot, bias_initializer=zeros,
+                       kernel_regularizer=None, bias_regularizer=None,
+                       activity_regularizer=None, kernel_constraint=None, bias_constraint=None)
+        elif node.kind == 'deconv':
+            # (keras/layers/convolutional.py Conv3DTranspose.get_config: Conv3D's keys without
+            # dilation_rate; output_padding arrived with Keras 2.2.3 and is not written)
+            cfg.update(filters=int(node.channels), kernel_size=[2, 2, 2], strides=[2, 2, 2],
+                       padding='valid', data_format='channels_last',
                        activation=a['activation'] or 'linear', use_bias=bool(a['use_bias']),
                        kernel_initializer=glorot, bias_initializer=zeros,
                        kernel_regularizer=None, bias_regularizer=None,

@@ -38,7 +38,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define FPL_ABI_VERSION 9
+#define FPL_ABI_VERSION 10
 
 typedef struct fpl_ctx fpl_ctx;
 typedef struct fpl_program fpl_program;
@@ -84,7 +84,13 @@ enum fpl_op_kind {
   FPL_OP_UP = 2,     /* UpSampling3D((p0,p1,p2)) nearest                     */
   FPL_OP_CROP = 3,   /* Cropping3D(((p0,p1),(p2,p3),(p4,p5)))                */
   FPL_OP_CONCAT = 4, /* concatenate([src0, src1]) on channels                */
-  FPL_OP_ADD = 5     /* act(src0 + src1)                                     */
+  FPL_OP_ADD = 5,    /* act(src0 + src1)                                     */
+  /* Conv3DTranspose(cout, 2, strides=2, 'valid'), the learned 2x up-convolution (k = 2,
+   * p0..p2 = 2): y[2i+a][2j+b][2k+c][co] = act(shift[co] + scale[co] * sum_ci
+   * x[i][j][k][ci] * W[a][b][c][co][ci]); kernel [8][cout][cin] (Keras memory order).
+   * fp32 executors only: the 16-bit / split precisions refuse a program that holds it.
+   * New in ABI 10 - a version 9 library does not know the kind, hence the bump */
+  FPL_OP_DECONV = 6
 };
 enum fpl_act { FPL_ACT_NONE = 0, FPL_ACT_RELU = 1, FPL_ACT_SIGMOID = 2 };
 
@@ -92,13 +98,13 @@ typedef struct fpl_op {
   int32_t kind;      /* fpl_op_kind                                          */
   int32_t src0, src1;/* tensor ids (0 = network input); src1 = -1 if unused  */
   int32_t dst;       /* tensor id produced                                   */
-  int32_t k;         /* conv kernel edge (1 or 3)                            */
+  int32_t k;         /* conv kernel edge (1 or 3); deconv: 2                 */
   int32_t cin, cout; /* channels in / out                                    */
   int32_t act;       /* fpl_act                                              */
   int64_t w_off;     /* offsets (floats) into the weight arena:              */
   int64_t scale_off; /*   kernel [k^3*cin][cout] (Keras memory order),       */
   int64_t shift_off; /*   scale[cout], shift[cout]                           */
-  int32_t p[6];      /* pool/up factors or crop pairs                        */
+  int32_t p[6];      /* pool/up factors, crop pairs or deconv strides        */
 } fpl_op;
 
 /* ---- context -------------------------------------------------------------- */
@@ -260,15 +266,21 @@ int fpl_v2o_copy_smoothed(fpl_ctx *ctx, float *dst, int dst_mem);
  * flypylib_amd/program.py (one entry per Keras layer). */
 enum fpl_layer_kind {
   FPL_L_CONV = 0, FPL_L_BN = 1, FPL_L_RELU = 2, FPL_L_POOL = 3, FPL_L_DROPOUT = 4,
-  FPL_L_UP = 5, FPL_L_CROP = 6, FPL_L_CONCAT = 7, FPL_L_ADD = 8
+  FPL_L_UP = 5, FPL_L_CROP = 6, FPL_L_CONCAT = 7, FPL_L_ADD = 8,
+  /* Conv3DTranspose(cout, 2, strides=2, 'valid') (FPL_OP_DECONV): k = 2, p0..p2 = 2, kernel
+   * [8][cout][cin] at w_off[0], bias at w_off[1]; act none or relu, under the rule stated
+   * for convolutions below.  Its gradients are sums in a fixed order (no float atomics), and
+   * in a network that holds it so are the convolutions' weight gradients: equal inputs give
+   * equal bits.  New in ABI 10 */
+  FPL_L_DECONV = 9
 };
 typedef struct fpl_layer {
   int32_t kind;        /* fpl_layer_kind                                       */
   int32_t src0, src1;  /* tensor ids (0 = network input)                       */
   int32_t dst;
-  int32_t k, cin, cout;/* conv                                                 */
-  int32_t use_bias;    /* conv                                                 */
-  int32_t act;         /* conv activation (fpl_act): relu on any conv but the
+  int32_t k, cin, cout;/* conv / deconv                                        */
+  int32_t use_bias;    /* conv / deconv                                        */
+  int32_t act;         /* conv / deconv activation (fpl_act): relu on any conv but the
                         * head (applied in the conv epilogue, its gradient masked
                         * in place in the backward pass; not in front of a BN),
                         * sigmoid on the head and only there                    */

@@ -70,6 +70,14 @@
             resident one; the four kernels of libfplroi.so alone (HIP events); BlockRoi.voxel_counts
             over the partition of a 4096^3 ROI on the host and with device=0; written to
             profiles/substacks.json
+  deconv    Conv3DTranspose(filters, 2, strides=2) (LayerGraph.deconv), all in one process, one
+            warm-up and then the median, min and max of 5: the example U-Net of
+            tests/deconv_cases.py (tiny_unet_t) inferring a resident 390^3 volume at tile 102
+            (pitch 96) on mfma_f32 and under FPL_FORCE_PEROP=1 with the per-kernel tables; its
+            training step at 8 x 62^3 patches (the fixed-order path of a network with the layer)
+            with the per-kernel table; and the deconv kernel alone (HIP events) at three shapes,
+            its achieved store bandwidth beside a device-to-device copy of the same byte count;
+            no gate; written to profiles/deconv.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -964,6 +972,118 @@ def substacks_bench(ctx, torch, n_tbars=32768, reps=5, host_reps=2):
     return row
 
 
+def _unet_t_102(in_sz=None):
+    """tests/deconv_cases.py's example U-Net at a production tile: 102 in, 96 out"""
+    from tests import deconv_cases as dc
+    return dc.tiny_unet_t_random((102,) * 3 if in_sz is None else in_sz)
+
+
+def deconv_bench(ctx, torch, vol=390, reps=5):
+    """the example U-Net with a Conv3DTranspose end to end, and the deconv kernel alone"""
+    from flypylib_amd import FplNetwork, _capi
+    from tests import deconv_cases as dc
+
+    def stats(v):
+        return {'median': round(float(np.median(v)), 4), 'min': round(float(min(v)), 4),
+                'max': round(float(max(v)), 4)}
+
+    def table():
+        return {k: {'ms': round(v['ms'], 4), 'launches': int(v['launches'])}
+                for k, v in sorted(ctx.timing_get().items(), key=lambda kv: -kv[1]['ms'])}
+    out = {'reps': reps, 'note': 'one warm-up, then median / min / max of %d; resident source and '
+                                 'destination; no gate: the path did not exist before' % reps}
+    # ---- the U-Net over a volume -------------------------------------------------------------
+    net = FplNetwork(_unet_t_102)
+    net._set_infer()
+    src = torch.from_numpy(np.random.default_rng(0).standard_normal((vol,) * 3).astype(np.float32)).to('cuda:0')
+    dst = torch.empty((vol,) * 3, dtype=torch.float32, device='cuda:0')
+    prog = net.infer_network.program
+    legs = {}
+    for leg, env in (('mfma_f32', None), ('perop_f32', '1')):
+        if env:
+            os.environ['FPL_FORCE_PEROP'] = env
+        try:
+            ms = []
+            for r in range(reps + 1):
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                prog.infer_volume(src, net.infer_sz, net.rf_offset, precision=_capi.PREC_F32, dst=dst,
+                                  dims=(vol,) * 3)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            path = ctx.last_path()
+            ctx.timing(True); ctx.timing_reset()
+            prog.infer_volume(src, net.infer_sz, net.rf_offset, precision=_capi.PREC_F32, dst=dst, dims=(vol,) * 3)
+            kern = table()
+            ctx.timing(False)
+        finally:
+            os.environ.pop('FPL_FORCE_PEROP', None)
+        legs[leg] = {'executor': path, 'ms': stats(ms[1:]), 'runs_ms': [round(x, 3) for x in ms[1:]],
+                     'mvox_s': round(vol ** 3 / np.median(ms[1:]) / 1e3, 1), 'kernels_one_pass': kern}
+        print(leg, json.dumps(legs[leg]['ms']), flush=True)
+    out['tiny_unet_t_infer'] = {'volume': [vol] * 3, 'tile_in': 102, 'pitch': 96, 'legs': legs}
+    # ---- its training step -------------------------------------------------------------------
+    batch, patch = 8, 62
+    g = dc.tiny_unet_t((patch,) * 3)[0]
+    rng = np.random.default_rng(1)
+    x = torch.from_numpy(rng.standard_normal((batch,) + (patch,) * 3 + (1,)).astype(np.float32)).to('cuda:0')
+    y = torch.from_numpy((rng.random((batch,) + (patch - 6,) * 3 + (1,)) < 0.3).astype(np.uint8)).to('cuda:0')
+    tr = _capi.Trainer(ctx, g)
+    ms = []
+    for r in range(reps + 1):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        tr.step(x, y, seed=r); tr.apply(1.0)
+        ctx.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    ctx.timing(True); ctx.timing_reset()
+    tr.step(x, y, seed=0); tr.apply(1.0)
+    ctx.synchronize()
+    kern = table()
+    ctx.timing(False)
+    tr.close()
+    out['tiny_unet_t_train_step'] = {
+        'batch': batch, 'patch': patch, 'ms': stats(ms[1:]), 'runs_ms': [round(v, 3) for v in ms[1:]],
+        'note': 'fixed-order path: plain fp32 weight-gradient kernels for every convolution and the deconv',
+        'kernels_one_step': kern}
+    print('train', json.dumps(out['tiny_unet_t_train_step']['ms']), flush=True)
+    # ---- the kernel alone ----------------------------------------------------------------------
+    alone = {}
+    for cin, cout, n, edge in ((16, 8, 8, 48), (48, 32, 2, 64), (96, 48, 2, 40)):
+        g, _ = dc.deconv_graph(cin, cout, 1, 1, 1, (edge,) * 3)
+        p = _capi.Program(ctx, g)
+        xin = torch.randn((n,) + (edge,) * 3, device='cuda:0')
+        yout = torch.empty((n,) + (2 * edge,) * 3 + (cout,), dtype=torch.float32, device='cuda:0')
+        k_ms = []
+        for r in range(reps + 1):
+            ctx.timing(True); ctx.timing_reset()
+            p.forward_device(xin, out=yout)
+            t = ctx.timing_get()
+            ctx.timing(False)
+            k_ms.append(t['mfma_deconv2_f32']['ms'])
+        p.close()
+        wr = yout.numel() * 4
+        rd = n * edge ** 3 * cin * 4
+        a_, b_ = torch.empty(wr // 4, device='cuda:0'), torch.empty(wr // 4, device='cuda:0')
+        c_ms = []
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            b_.copy_(a_)
+            e1.record(); e1.synchronize()
+            c_ms.append(e0.elapsed_time(e1))
+        del a_, b_, xin, yout
+        km, cm = float(np.median(k_ms[1:])), float(np.median(c_ms[1:]))
+        alone['%dto%d_%dx%d' % (cin, cout, n, edge)] = {
+            'input_voxels': n * edge ** 3, 'bytes_written': wr, 'bytes_read': rd,
+            'kernel_ms': stats(k_ms[1:]), 'store_gb_s': round(wr / km / 1e6, 1),
+            'd2d_copy_same_bytes_ms': stats(c_ms[1:]),
+            'd2d_copy_gb_s_written': round(wr / cm / 1e6, 1),
+            'kernel_over_copy': round(km / cm, 3)}
+        print(json.dumps(alone['%dto%d_%dx%d' % (cin, cout, n, edge)]), flush=True)
+    out['deconv_kernel_alone'] = alone
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
@@ -1197,6 +1317,11 @@ def main():
         res['substacks'] = substacks_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'substacks.json')
+
+    if 'deconv' in what:
+        res['deconv'] = deconv_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'deconv.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
