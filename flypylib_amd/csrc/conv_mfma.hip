@@ -796,6 +796,97 @@ __global__ __launch_bounds__(256) void FPLK(conv1)(Conv1Args a) {
   if (SPLIT) ovf_commit(ovf, a.flag, FPL_RANGE_UNET);
 }
 
+// ---- Conv3DTranspose(16*MB, 2, strides=2) as eight voxel GEMMs --------------------------------
+// No two taps of a 2x2x2 stride-2 transposed convolution meet in an output voxel: input voxel
+// (z, y, x) of a tile and tap (ta, tb, tc) give output voxel (2z + ta, 2y + tb, 2x + tc) of the
+// same tile and nothing else does.  So the layer is conv1's voxel GEMM eight times over the SAME
+// B fragments (loaded once per group of 16 input voxels), each tap with a fragment set of its own
+// (gx_exec.h packs one conv1 set per tap: [tap][K-step][set][mb]) and a store at its own place.
+//
+// Where the taps' fragments live: a workgroup keeps TPB taps in LDS and blockIdx.y picks which -
+// TPB = the most taps whose sets fit 64 KiB (two workgroups per CU, as conv1's widest instance),
+// so 32 -> 32 holds all eight in every build and reads its input once, and the split 128 -> 64
+// instance (64 KiB per tap) holds one and reads its input eight times (DESIGN.md section 19 has
+// the table).  The re-read input is CIN channels per voxel against 8 x 16 MB written.
+struct Deconv2Args {
+  const h16_t *in; int64_t M;   // n * din^3 input voxels in chunk planes of M * 32 (`plane`)
+  int64_t plane;
+  const unsigned char *w;        // [tap][kstep][set][mb] fragments (a conv1 set per tap)
+  const float *shift;
+  h16_t *out;                   // n tiles of (2 din)^3 voxels
+  int64_t oplane;                // elements of one chunk plane of `out`
+  int din, relu;
+  unsigned *flag;                // split build: half-range guard
+};
+
+template <int CIN, int MB> struct Deconv2Geo {
+  static constexpr int KS = CIN / RCH;
+  static constexpr int WMB = PM * MB;
+  static constexpr int NF = KS * WMB;                     // KiB of fragments per tap
+  static constexpr int TPB = NF * 8 <= 64 ? 8 : NF * 4 <= 64 ? 4 : NF * 2 <= 64 ? 2 : 1;  // taps per workgroup
+  static constexpr int SMEM = TPB * NF * 1024;
+  static_assert(NF <= 64, "a tap's fragments fit 64 KiB");
+};
+
+template <int CIN, int MB>
+__global__ __launch_bounds__(256) void FPLK(deconv2)(Deconv2Args a) {
+  using G = Deconv2Geo<CIN, MB>;
+  constexpr int KS = G::KS, WMB = G::WMB, NF = G::NF, TPB = G::TPB;
+  __shared__ __attribute__((aligned(16))) unsigned char wl[G::SMEM];   // TPB * NF KiB of fragments
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int tap0 = blockIdx.y * TPB;
+  for (int i = tid; i < TPB * NF * 64; i += 256)
+    reinterpret_cast<u32x4 *>(wl)[i] = reinterpret_cast<const u32x4 *>(a.w)[(int64_t)tap0 * NF * 64 + i];
+  f32x4 sh[MB];
+#pragma unroll
+  for (int b = 0; b < MB; ++b)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sh[b][r] = a.shift[4 * MB * g + 4 * b + r];
+  __syncthreads();
+  const int64_t groups = (a.M + 15) / 16;
+  const int d3 = a.din * a.din * a.din, dout = 2 * a.din;
+  unsigned ovf = 0u;
+  for (int64_t grp = (int64_t)blockIdx.x * 4 + wave; grp < groups; grp += (int64_t)gridDim.x * 4) {
+    int64_t m = grp * 16 + c;
+    const bool ok = m < a.M;                        // (clamped lanes compute and store nothing)
+    m = ok ? m : a.M - 1;
+    h16x8 bf[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+      bf[s] = *reinterpret_cast<const h16x8 *>(a.in + s * a.plane + m * CC + 8 * g);
+    // the voxel's tile and its place there (groups straddle rows, planes and tiles)
+    const int64_t t = m / d3;
+    unsigned r = (unsigned)(m - t * d3);
+    const int x = (int)(r % (unsigned)a.din); r /= (unsigned)a.din;
+    const int y = (int)(r % (unsigned)a.din), z = (int)(r / (unsigned)a.din);
+    const int64_t ov0 = ((t * dout + 2 * z) * dout + 2 * y) * (int64_t)dout + 2 * x;
+    for (int tp = 0; tp < TPB; ++tp) {
+      // (as conv1: keeps the fragment reads, the same in every trip, inside the loops)
+      int zero = 0;
+      asm volatile("" : "+s"(zero));
+      const unsigned char *wq = wl + zero + tp * (NF * 1024);
+      f32x4 acc[MB];
+#pragma unroll
+      for (int b = 0; b < MB; ++b) {
+        acc[b] = sh[b];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          acc[b] = mfma16(*reinterpret_cast<const h16x8 *>(wq + ((s * WMB + b) * 64 + lane) * 16),
+                          bf[s], acc[b]);
+          if (SPLIT)
+            acc[b] = mfma16(*reinterpret_cast<const h16x8 *>(wq + ((s * WMB + MB + b) * 64 + lane) * 16),
+                            bf[s], acc[b]);
+        }
+      }
+      const int tap = tap0 + tp;
+      const int64_t ov = ov0 + ((int64_t)(tap >> 2) * dout + ((tap >> 1) & 1)) * dout + (tap & 1);
+      if (ok) store_il<MB, false>(a.out + ov * CC, a.oplane, g, acc, a.relu, ovf);
+    }
+  }
+  if (SPLIT) ovf_commit(ovf, a.flag, FPL_RANGE_UNET);
+}
+
 // ---- unet_like's first stage (fplmodels.py:210-256): conv3 1->32 +BN+ReLU, conv1 32->32
 // +BN+ReLU chained in registers (with interleaved rows the packed output of the first is
 // the K-step of the second), stored as c1 and max-pooled to p1.  Block 4 x 4 x 16 voxels,

@@ -3,7 +3,8 @@
 // match_unet knows - baseline_model, resnet_like, unet_like4b, unet_like_vol
 // (reference flypylib/fplmodels.py:73-100, 174-208, 410-467, 470-526) - run op by op on the same
 // descriptor-driven kernels: conv3 (any mix of plain / upsampled / cropped 16-channel source chunks,
-// 32 or 64 outputs per launch, optional fused MaxPooling3D), conv1 (voxel GEMM), pool2_h16, and three
+// 32 or 64 outputs per launch, optional fused MaxPooling3D), conv1 (voxel GEMM), deconv2 (a
+// Conv3DTranspose(filters, 2, strides=2): eight voxel GEMMs, each stored at its tap's place), pool2_h16, and three
 // small kernels of this file: the stand-alone first layer (conv3 1 -> C), Add (+ReLU) of a cropped
 // shortcut, and the 1x1x1 -> 1 sigmoid head, which takes the hi + lo halves back to fp32 and writes the
 // prediction volume (UpSampling3D(rf_stride) on store).
@@ -14,6 +15,7 @@
 // are zero too.  UpSampling3D, Cropping3D and concatenate never materialise: they are resolved into the
 // source descriptors of the convolution that reads them (and the crop of a shortcut into Add's indexing).
 #pragma once
+#include "deconv_pack.h"
 
 struct GxView { int base, ups, crop; };   // a materialised tensor seen through at most one UP or CROP
 
@@ -78,7 +80,7 @@ bool gx_views(const fpl_program *prog, const GxPlan &pl, int t, std::vector<GxVi
   if (pi < 0) { out->push_back(GxView{t, 0, 0}); return t == 0; }
   const fpl_op &op = prog->ops[pi];
   switch (op.kind) {
-    case FPL_OP_CONV: case FPL_OP_POOL: case FPL_OP_ADD:
+    case FPL_OP_CONV: case FPL_OP_POOL: case FPL_OP_ADD: case FPL_OP_DECONV:
       out->push_back(GxView{t, 0, 0});
       return true;
     case FPL_OP_UP: case FPL_OP_CROP: {
@@ -216,16 +218,27 @@ bool gx_match(const fpl_program *prog) {
           int b;
           if (!gx_plain(prog, pl, op.src0, &b)) return false;
           const int ci = gx_pad32(op.cin), co = gx_pad32(op.cout);
-          if ((ci != 32 && ci != 64 && ci != 128) || (co != 32 && co != 64)) return false;
+          // (96 outputs from 32 or 64 inputs: the one producer of a 96-channel tensor, which a Conv3DTranspose,
+          // a 3x3x3 convolution, a pool, an Add and the head read)
+          if ((ci != 32 && ci != 64 && ci != 128) || (co != 32 && co != 64 && !(co == 96 && ci <= 64))) return false;
           if (op.act != FPL_ACT_RELU && op.act != FPL_ACT_NONE) return false;
         } else {
           return false;
         }
         break;
       }
+      case FPL_OP_DECONV: {                              // eight voxel GEMMs: conv1's widths
+        int b;
+        if (op.k != 2 || op.p[0] != 2 || op.p[1] != 2 || op.p[2] != 2 || !gx_plain(prog, pl, op.src0, &b)) return false;
+        const int ci = gx_pad32(op.cin), co = gx_pad32(op.cout);
+        if ((ci != 32 && ci != 64 && ci != 96 && ci != 128) || (co != 32 && co != 64)) return false;
+        if (op.act != FPL_ACT_RELU && op.act != FPL_ACT_NONE) return false;
+        break;
+      }
       case FPL_OP_POOL: {
         int b;
         if (op.p[0] != 2 || op.p[1] != 2 || op.p[2] != 2 || !gx_plain(prog, pl, op.src0, &b)) return false;
+        // (a pool directly on a Conv3DTranspose is declined here too)
         const fpl_op &src = prog->ops[pl.prod[b]];       // pool2_h16 takes values >= 0
         if ((src.kind != FPL_OP_CONV && src.kind != FPL_OP_ADD) || src.act != FPL_ACT_RELU) return false;
         break;
@@ -514,10 +527,32 @@ int gx_prepare(fpl_ctx *ctx, fpl_program *prog, const GxPlan &pl, GxState **out)
   st->conv.assign(prog->ops.size(), GxConvW());
   for (size_t i = 0; i < prog->ops.size(); ++i) {
     const fpl_op &op = prog->ops[i];
-    if (op.kind != FPL_OP_CONV) continue;
+    if (op.kind != FPL_OP_CONV && op.kind != FPL_OP_DECONV) continue;
     GxConvW &cw = st->conv[i];
     std::vector<uint16_t> f;
     cw.off_s = shifts.size();
+    if (op.kind == FPL_OP_DECONV) {
+      // per tap the padded 1x1x1 convolution its [cout][cin] slice is (deconv_pack.h), scale folded in by the
+      // packer: [tap][K-step][set][mb], one conv1 set per tap; the scan below covers them like any fragment
+      const int cin_p = gx_pad32(op.cin), cout_p = gx_pad32(op.cout);
+      std::vector<float> Ap((size_t)cin_p * cout_p + 2 * (size_t)cout_p);
+      fpl_op opp = op;
+      opp.kind = FPL_OP_CONV; opp.k = 1; opp.cin = cin_p; opp.cout = cout_p; opp.w_off = 0;
+      opp.scale_off = (int64_t)cin_p * cout_p; opp.shift_off = opp.scale_off + cout_p;
+      for (int tap = 0; tap < 8; ++tap) {
+        fpl_deconv_tap_arena(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, tap, cin_p, cout_p,
+                             Ap.data());
+        std::vector<uint16_t> ft;
+        pack_conv1(Ap.data(), opp, true, &ft);
+        f.insert(f.end(), ft.begin(), ft.end());
+      }
+      cw.cin_p = cin_p; cw.cout_p = cout_p;
+      shifts.insert(shifts.end(), Ap.begin() + opp.shift_off, Ap.begin() + opp.shift_off + cout_p);
+      while (shifts.size() % 4) shifts.push_back(0.f);
+      cw.off_w = all.size() * sizeof(uint16_t);
+      all.insert(all.end(), f.begin(), f.end());
+      continue;
+    }
     if (op.k == 1 && op.cout == 1) {                       // head: fp32 weights [C] (scale folded in), then the bias
       for (int ci = 0; ci < op.cin; ++ci) shifts.push_back(A[op.w_off + ci] * A[op.scale_off]);
       shifts.push_back(A[op.shift_off]);
@@ -577,7 +612,7 @@ int gx_prepare(fpl_ctx *ctx, fpl_program *prog, const GxPlan &pl, GxState **out)
       } else {
         for (int r = 0; r < gx_pad32(op.cin); ++r) rows.push_back(r < op.cin ? r : -1);
       }
-      const int cout_p = op.cout > 64 ? op.cout : gx_pad32(op.cout);
+      const int cout_p = op.k == 3 && op.cout > 64 ? op.cout : gx_pad32(op.cout);
       std::vector<float> Ap;
       fpl_op opp;
       gx_padded_op(A, op, rows, cout_p, &Ap, &opp);
@@ -681,6 +716,15 @@ void gx_launch_conv1(fpl_ctx *ctx, Conv1Args &a) {
   }
   const unsigned grid = (unsigned)std::min<int64_t>(ceil_div64(a.M, 64), (int64_t)ctx->n_cu * 8);
   FPLK(conv1)<CIN, MB, 0><<<grid, 256, SMEM, ctx->stream>>>(a);
+}
+
+template <int CIN, int MB>
+void gx_launch_deconv2(fpl_ctx *ctx, Deconv2Args &a) {
+  using G = Deconv2Geo<CIN, MB>;
+  // persistent over groups of 16 voxels; blockIdx.y = which TPB taps
+  constexpr int NY = 8 / G::TPB;
+  const unsigned gx = (unsigned)std::min<int64_t>(ceil_div64(a.M, 64), std::max<int64_t>((int64_t)ctx->n_cu * 4 / NY, 1));
+  FPLK(deconv2)<CIN, MB><<<dim3(gx, NY), 256, 0, ctx->stream>>>(a);
 }
 
 int gx_forward(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T, float *out, const FplTileIO *io) {
@@ -895,12 +939,39 @@ int gx_forward(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T, f
           switch (key) {
             case 32032: gx_launch_conv1<32, 2>(ctx, a); break;
             case 32064: gx_launch_conv1<32, 4>(ctx, a); break;
+            case 32096: gx_launch_conv1<32, 6>(ctx, a); break;
+            case 64096: gx_launch_conv1<64, 6>(ctx, a); break;
             case 64032: gx_launch_conv1<64, 2>(ctx, a); break;
             case 64064: gx_launch_conv1<64, 4>(ctx, a); break;
             case 128032: gx_launch_conv1<128, 2>(ctx, a); break;
             case 128064: gx_launch_conv1<128, 4>(ctx, a); break;
             default: return fpl_fail(ctx, "gx: no conv1 kernel for %d -> %d channels", cw.cin_p, cw.cout_p);
           }
+        }
+        break;
+      }
+      case FPL_OP_DECONV: {
+        int b;
+        FPL_REQUIRE(ctx, gx_plain(prog, pl, op.src0, &b) && buf[b], "gx: deconv input");
+        FPL_REQUIRE(ctx, dim[op.dst] == 2 * dim[b] && cp[b] == cw.cin_p && dim[b] <= 1024, "gx: deconv shapes");
+        FPL_TRY(balloc(op.dst));
+        FPL_REQUIRE(ctx, cp[op.dst] == cw.cout_p, "gx: deconv widths");
+        Deconv2Args a;
+        a.in = buf[b]; a.M = (int64_t)n * cube(dim[b]); a.plane = a.M * CC;
+        a.w = F + cw.off_w; a.shift = S + cw.off_s;
+        a.out = buf[op.dst]; a.oplane = plane(op.dst);
+        a.din = dim[b]; a.relu = op.act == FPL_ACT_RELU; a.flag = flag;
+        TimedLaunch tl(ctx, "gx_deconv2");
+        switch (cw.cin_p * 1000 + cw.cout_p) {
+          case 32032: gx_launch_deconv2<32, 2>(ctx, a); break;
+          case 32064: gx_launch_deconv2<32, 4>(ctx, a); break;
+          case 64032: gx_launch_deconv2<64, 2>(ctx, a); break;
+          case 64064: gx_launch_deconv2<64, 4>(ctx, a); break;
+          case 96032: gx_launch_deconv2<96, 2>(ctx, a); break;
+          case 96064: gx_launch_deconv2<96, 4>(ctx, a); break;
+          case 128032: gx_launch_deconv2<128, 2>(ctx, a); break;
+          case 128064: gx_launch_deconv2<128, 4>(ctx, a); break;
+          default: return fpl_fail(ctx, "gx: no deconv2 kernel for %d -> %d channels", cw.cin_p, cw.cout_p);
         }
         break;
       }

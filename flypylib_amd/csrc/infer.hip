@@ -100,6 +100,12 @@ bool has_deconv(const fpl_program *prog) {
   return false;
 }
 
+// does one of the three builds of conv_mfma.hip run this program at this precision?
+bool h16_executor_takes(const fpl_program *prog, int precision) {
+  return fpl_unet_fast_available_bf16(prog, precision) || fpl_unet_fast_available_f16(prog, precision) ||
+         fpl_unet_fast_available_f16s(prog, precision);
+}
+
 // may neighbouring tiles of the reference lattice be computed as one larger tile with the
 // same results?  (no upsampling: then the output's stride is the deepest pooling level;
 // every pool sees even extents; the lattice pitch is a multiple of the stride)
@@ -255,12 +261,15 @@ static int infer_volume_impl(fpl_ctx *ctx, fpl_program *prog, const void *src,
     dst_dev = (float *)p;
     dst_base = wr_lo;
   }
-  FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_deconv(prog),
-              "fpl_infer_volume: no 16-bit MFMA kernels for the layer Conv3DTranspose: this network runs in "
-              "fp32 only; use precision f32 (or 'auto')");
   // the fused fast path writes every valid voxel itself: only the border shell
   // needs clearing there; the per-op path stitches tiles into a zeroed volume
   const bool cubic = tile_in[0] == tile_in[1] && tile_in[1] == tile_in[2];
+  // (a Conv3DTranspose has 16-bit / split-half kernels on the graph executor only: gx_exec.h)
+  FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_deconv(prog) || (cubic && h16_executor_takes(prog, precision)),
+              "fpl_infer_volume: the 16-bit / split-half graph executor does not take this program's "
+              "Conv3DTranspose (2 x 2 x 2, strides 2, up to 128 -> 64 channels, on a convolution's, pool's or "
+              "add's output, not under a pool, on cubic tiles; no 1x1x1 convolution on a concatenation): it runs "
+              "in fp32; use precision f32 (or 'auto')");
   const bool unet_split_ok = cubic && fpl_unet_fast_available_f16s(prog, FPL_PREC_F16S);
   const bool split = fpl_split_path_available(prog, precision, offset, out_sz);
   FPL_REQUIRE(ctx, precision != FPL_PREC_F16S || split || unet_split_ok,
@@ -652,9 +661,9 @@ int fpl_infer_volume(fpl_ctx *ctx, fpl_program *prog, const void *src,
     int32_t out_sz[3];
     for (int a = 0; a < 3; ++a) out_sz[a] = tile_in[a] - 2 * offset[a];
     const bool cubic = tile_in[0] == tile_in[1] && tile_in[1] == tile_in[2];
-    const bool have_split = !has_deconv(prog) &&
-                            (fpl_split_path_available(prog, FPL_PREC_F16S, offset, out_sz) ||
-                             (cubic && fpl_unet_fast_available_f16s(prog, FPL_PREC_F16S)));
+    // (a program with a Conv3DTranspose like any other: the graph executor takes it or it does not)
+    const bool have_split = fpl_split_path_available(prog, FPL_PREC_F16S, offset, out_sz) ||
+                            (cubic && fpl_unet_fast_available_f16s(prog, FPL_PREC_F16S));
     if (have_split && prog->half_range_bad_version != prog->arena_version) {
       const int rc = run(FPL_PREC_F16S, &bits);
       if (rc == 0 && !bits) return 0;

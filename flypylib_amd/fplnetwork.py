@@ -235,7 +235,8 @@ class FplNetwork:
         fastest executor that delivers them - split IEEE halves ('f16s': within ~4e-6 of
         fp32, the same detected point set) for all ten factories of fplmodels (the fused
         kernels of vgg_like / vgg_like2 / the U-Net skeletons, the layer-by-layer graph
-        executor for the others), rerun on the fp32 MFMA kernels when a weight, an input
+        executor for the others and for a caller's own layer program, a Conv3DTranspose of
+        up to 128 -> 64 channels included), rerun on the fp32 MFMA kernels when a weight, an input
         voxel or an activation leaves the IEEE-half range (the kernels check), and the fp32
         MFMA kernels ('f32') for layer programs neither has kernels for; 'f16' / 'bf16' =
         plain 16-bit operands (up to ~1e-3 / ~8e-3 off fp32 on trained weights, 2 - 3x faster

@@ -88,7 +88,9 @@ enum fpl_op_kind {
   /* Conv3DTranspose(cout, 2, strides=2, 'valid'), the learned 2x up-convolution (k = 2,
    * p0..p2 = 2): y[2i+a][2j+b][2k+c][co] = act(shift[co] + scale[co] * sum_ci
    * x[i][j][k][ci] * W[a][b][c][co][ci]); kernel [8][cout][cin] (Keras memory order).
-   * fp32 executors only: the 16-bit / split precisions refuse a program that holds it.
+   * The 16-bit / split precisions run it where the graph executor takes the program (up to
+   * 128 -> 64 channels, on a materialised tensor, not under a pool) and refuse the program
+   * with the layer named otherwise; fp32 runs it always.
    * New in ABI 10 - a version 9 library does not know the kind, hence the bump */
   FPL_OP_DECONV = 6
 };

@@ -77,7 +77,10 @@
             training step at 8 x 62^3 patches (the fixed-order path of a network with the layer)
             with the per-kernel table; and the deconv kernel alone (HIP events) at three shapes,
             its achieved store bandwidth beside a device-to-device copy of the same byte count;
-            no gate; written to profiles/deconv.json
+            then the layer on the split-half graph executor: tests/deconv_gx_cases.py's unet_t3
+            over the same volume at tile 102 (pitch 94) under 'auto' and under precision 'f32'
+            with the per-kernel tables and their ratio, and gx_deconv2 alone at the same three
+            shapes ('f16s' and 'f16'); no gate; written to profiles/deconv.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -1081,7 +1084,74 @@ def deconv_bench(ctx, torch, vol=390, reps=5):
             'kernel_over_copy': round(km / cm, 3)}
         print(json.dumps(alone['%dto%d_%dx%d' % (cin, cout, n, edge)]), flush=True)
     out['deconv_kernel_alone'] = alone
+    out.update(deconv_gx_bench(ctx, torch, vol, reps, stats, table, alone))
     return out
+
+
+def _unet_t3_102(in_sz=None):
+    """tests/deconv_gx_cases.py's example U-Net (the graph executor takes it) at tile 102: 94 out"""
+    from tests import deconv_gx_cases as gc
+    return gc.unet_t3_random((102,) * 3 if in_sz is None else in_sz)
+
+
+def deconv_gx_bench(ctx, torch, vol, reps, stats, table, alone):
+    """the layer on the split-half graph executor: unet_t3 under 'auto' against precision 'f32' of the
+    same network in the same process, and gx_deconv2 alone at the fp32 kernel's three shapes"""
+    from flypylib_amd import FplNetwork, _capi
+    from tests import deconv_gx_cases as gc
+    net = FplNetwork(_unet_t3_102)
+    net._set_infer()
+    src = torch.from_numpy(np.random.default_rng(0).standard_normal((vol,) * 3).astype(np.float32)).to('cuda:0')
+    dst = torch.empty((vol,) * 3, dtype=torch.float32, device='cuda:0')
+    prog = net.infer_network.program
+    legs = {}
+    for leg, prec in (('auto', _capi.PREC_AUTO), ('f32', _capi.PREC_F32)):
+        ms = []
+        for r in range(reps + 1):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            prog.infer_volume(src, net.infer_sz, net.rf_offset, precision=prec, dst=dst, dims=(vol,) * 3)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        path = ctx.last_path()
+        ctx.timing(True); ctx.timing_reset()
+        prog.infer_volume(src, net.infer_sz, net.rf_offset, precision=prec, dst=dst, dims=(vol,) * 3)
+        kern = table()
+        ctx.timing(False)
+        legs[leg] = {'executor': path, 'ms': stats(ms[1:]), 'runs_ms': [round(x, 3) for x in ms[1:]],
+                     'mvox_s': round(vol ** 3 / np.median(ms[1:]) / 1e3, 1), 'kernels_one_pass': kern}
+        print('unet_t3', leg, path, json.dumps(legs[leg]['ms']), flush=True)
+    res = {'unet_t3_infer': {
+        'volume': [vol] * 3, 'tile_in': 102, 'pitch': 94, 'legs': legs,
+        'f32_over_auto': round(legs['f32']['ms']['median'] / legs['auto']['ms']['median'], 3)}}
+    del src, dst
+    # ---- gx_deconv2 alone: the layer behind a first layer and a pool, n tiles of edge^3 input voxels ------
+    rows = {}
+    for cin, cout, n, edge in ((16, 8, 8, 48), (48, 32, 2, 64), (96, 48, 2, 40)):
+        g, off = gc.layer_alone(cin, cout, 1, 'relu', edge=edge)
+        tile = gc.tile_of(cin, edge)
+        p = _capi.Program(ctx, g, (1, 1, 1))
+        shape = (n * (tile - 2 * off) + 2 * off, tile, tile)
+        u8 = np.random.default_rng(1).integers(0, 256, shape, dtype=np.uint8)     # (kernel times only: a host source)
+        row = {'input_voxels': n * edge ** 3}
+        for kind, prec in (('f16s', _capi.PREC_F16S), ('f16', _capi.PREC_F16)):
+            k_ms = []
+            for r in range(reps + 1):
+                ctx.timing(True); ctx.timing_reset()
+                p.infer_volume(u8, (tile,) * 3, (off,) * 3, mean=128.0, std=33.0, precision=prec)
+                t = ctx.timing_get()
+                ctx.timing(False)
+                k_ms.append(t['gx_deconv2']['ms'])
+            wr = n * (2 * edge) ** 3 * ((cout + 31) // 32 * 32) * (4 if kind == 'f16s' else 2)
+            row[kind] = {'executor': ctx.last_path(), 'kernel_ms': stats(k_ms[1:]), 'bytes_written': wr,
+                         'store_gb_s': round(wr / float(np.median(k_ms[1:])) / 1e6, 1)}
+        f32 = alone.get('%dto%d_%dx%d' % (cin, cout, n, edge))
+        if f32:
+            row['f32_kernel_over_f16s'] = round(f32['kernel_ms']['median'] / row['f16s']['kernel_ms']['median'], 3)
+        p.close()
+        rows['%dto%d_%dx%d' % (cin, cout, n, edge)] = row
+        print('gx_deconv2', cin, cout, json.dumps(row), flush=True)
+    res['gx_deconv2_alone'] = rows
+    return res
 
 
 def main():
