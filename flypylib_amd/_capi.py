@@ -15,7 +15,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 MEM_DEVICE_BOX = 2           # fpl_v2o_set_seg: `seg` is a fpl_seg_box
 U8, F32, F64 = 0, 1, 2
 PREC_AUTO, PREC_F32, PREC_BF16, PREC_F16, PREC_F16S = -1, 0, 1, 2, 3
-ABI_VERSION = 10
+ABI_VERSION = 11
 COMM_ID_BYTES = 128
 
 

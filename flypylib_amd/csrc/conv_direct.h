@@ -1,4 +1,4 @@
-// Direct fp32 conv / transposed-conv kernels shared by the per-op inference executor (generic.hip)
+// Direct fp32 conv / transposed-conv / strided-conv kernels shared by the per-op inference executor (generic.hip)
 // and the training engine (train.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,5 +72,31 @@ static __global__ __launch_bounds__(256) void deconv2_direct_f32(
   const float *wp = w + ((int64_t)tap * cout + co) * cin;
   float acc = 0.f;
   for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[ci], acc);
+  y[i] = apply_act(fmaf(acc, scale[co], shift[co]), act);
+}
+
+// Direct Conv3D(cout, 2, strides=2, 'valid'): the readable restatement of FPL_OP_DOWN.  One
+// thread = one output element, eight taps of cin products each in (a, b, c, ci) order.
+// x (n, D, H, W, cin), w [8][cin][cout], y (n, D/2, H/2, W/2, cout); an odd axis drops its last
+// input plane.
+static __global__ __launch_bounds__(256) void down2_direct_f32(
+    const float *__restrict__ x, const float *__restrict__ w,
+    const float *__restrict__ scale, const float *__restrict__ shift,
+    float *__restrict__ y, int64_t n_out, int D, int H, int W, int cin, int cout, int act) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  const int od = D / 2, oh = H / 2, ow = W / 2;
+  int64_t t = i;
+  const int co = (int)(t % cout); t /= cout;
+  const int ox = (int)(t % ow); t /= ow;
+  const int oy = (int)(t % oh); t /= oh;
+  const int oz = (int)(t % od); t /= od;
+  float acc = 0.f;
+  for (int tap = 0; tap < 8; ++tap) {
+    const float *xp = x + ((((t * D + 2 * oz + (tap >> 2)) * H + 2 * oy + ((tap >> 1) & 1)) * (int64_t)W +
+                            2 * ox + (tap & 1)) * cin);
+    const float *wp = w + (int64_t)tap * cin * cout + co;
+    for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[(int64_t)ci * cout], acc);
+  }
   y[i] = apply_act(fmaf(acc, scale[co], shift[co]), act);
 }

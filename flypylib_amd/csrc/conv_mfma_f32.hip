@@ -985,6 +985,142 @@ __global__ __launch_bounds__(256) void deconv2_f32(DeconvF a) {
   }
 }
 
+// ---- Conv3D(cout, 2, strides 2, 'valid') as a voxel GEMM (fp32) -----------------------
+// No two windows overlap: M = output voxels, K = 8 * cin, N = cout.  For a fixed (a, b) the
+// two x taps of an output voxel are 2 * cin consecutive floats of the channels-last input, so
+// K is ordered [ab][c * cin + ci]: four segments of 2 * cin, each padded to whole K-blocks of
+// 16, each ONE contiguous read per output voxel.  The weights are the A operand (rows = output
+// channels), the voxels the B operand: lane (c, g) ends up with four consecutive channels of
+// voxel c - one 16-B store when cout is a multiple of 4.  Per output voxel the kernel reads
+// 8 * cin floats and writes cout: it is bound by its loads.  An odd axis drops its last input
+// plane: 2 * (s / 2) - 1 is the last index read.
+// NKB > 0 (cin <= 8 * NKB): the 4 x NKB input quads of each of a lane's G voxels stay in
+// registers for all N-blocks; NKB = 0: any cin, the quads are re-read (from L1) for every NBT
+// N-blocks.  The fragments are padded to a multiple of NBT N-blocks (zeros, never stored).
+struct DownF {
+  const float *in; int cin;                // (n, D, H, W, cin)
+  int D, H, W;
+  int64_t M;                               // output voxels n * OD * OH * OW
+  int OD, OH, OW;
+  const float *w;                          // fragments [ab][kb][nb][lane][4], scale folded in
+  const float *shift;                      // [16 * nbp]
+  int act;
+  float *out; int cout;                    // (n, OD, OH, OW, cout)
+  int nbp;                                 // N-blocks, padded: a multiple of NBT
+};
+
+// four consecutive floats of a tap pair's 2 * cin from `ch` on, zero beyond; `vec`: cin is a
+// multiple of 4, so every voxel starts on 16 bytes and no quad straddles the end.  No
+// divergent branch: a lane outside reads a valid address of its pair and drops the value
+__device__ __forceinline__ f32x4 load_pair_quad(const float *pair, int k2, int ch, bool vec) {
+  f32x4 bf;
+  if (vec) {
+    const bool inside = ch < k2;
+    bf = *reinterpret_cast<const f32x4 *>(pair + (inside ? ch : 0));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bf[q] = inside ? bf[q] : 0.f;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool inside = ch + q < k2;
+      const float v = pair[inside ? ch + q : 0];
+      bf[q] = inside ? v : 0.f;
+    }
+  }
+  return bf;
+}
+
+template <int NKB, int G, int NBT>
+__global__ __launch_bounds__(256) void down2_f32(DownF a) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int k2 = 2 * a.cin;
+  const int nkb = NKB ? NKB : (k2 + 15) / 16;
+  const bool vec = (a.cin & 3) == 0;                       // wave-uniform
+  const int64_t xrow = (int64_t)a.W * a.cin;               // floats per input x row
+  const int64_t groups = (a.M + 16 * G - 1) / (16 * G);
+  for (int64_t grp = (int64_t)blockIdx.x * 4 + wave; grp < groups; grp += (int64_t)gridDim.x * 4) {
+    const float *xin[G];
+    int64_t mo[G];
+    bool ok[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      int64_t mm = (grp * G + q) * 16 + c;
+      ok[q] = mm < a.M;
+      mm = ok[q] ? mm : a.M - 1;
+      mo[q] = mm;
+      int64_t t = mm;
+      const int x = (int)(t % a.OW); t /= a.OW;
+      const int y = (int)(t % a.OH); t /= a.OH;
+      const int z = (int)(t % a.OD); t /= a.OD;
+      xin[q] = a.in + ((t * a.D + 2 * z) * a.H + 2 * y) * xrow + (int64_t)2 * x * a.cin;
+    }
+    f32x4 bf[G][4][NKB ? NKB : 1];
+    if (NKB) {
+#pragma unroll
+      for (int q = 0; q < G; ++q)
+#pragma unroll
+        for (int ab = 0; ab < 4; ++ab)
+#pragma unroll
+          for (int kb = 0; kb < (NKB ? NKB : 1); ++kb)
+            bf[q][ab][kb] = load_pair_quad(xin[q] + ((ab >> 1) * a.H + (ab & 1)) * xrow, k2, 16 * kb + 4 * g, vec);
+    }
+#pragma unroll 1
+    for (int nb0 = 0; nb0 < a.nbp; nb0 += NBT) {
+      f32x4 acc[G][NBT];
+#pragma unroll
+      for (int t = 0; t < NBT; ++t) {
+        const f32x4 sh = *reinterpret_cast<const f32x4 *>(a.shift + 16 * (nb0 + t) + 4 * g);
+#pragma unroll
+        for (int q = 0; q < G; ++q) acc[q][t] = sh;
+      }
+      if (NKB) {
+#pragma unroll
+        for (int ab = 0; ab < 4; ++ab)
+#pragma unroll
+          for (int kb = 0; kb < (NKB ? NKB : 1); ++kb) {
+            const float *wp = a.w + (((int64_t)(ab * nkb + kb) * a.nbp + nb0) * 64 + lane) * 4;
+            f32x4 wf[NBT];
+#pragma unroll
+            for (int t = 0; t < NBT; ++t) wf[t] = *reinterpret_cast<const f32x4 *>(wp + t * 256);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int t = 0; t < NBT; ++t)
+#pragma unroll
+                for (int q = 0; q < G; ++q) acc[q][t] = mfma4(wf[t][j], bf[q][ab][kb][j], acc[q][t]);
+          }
+      } else {
+#pragma unroll 1
+        for (int ab = 0; ab < 4; ++ab) {
+          const int64_t aboff = ((ab >> 1) * a.H + (ab & 1)) * xrow;
+          for (int kb = 0; kb < nkb; ++kb) {
+            const float *wp = a.w + (((int64_t)(ab * nkb + kb) * a.nbp + nb0) * 64 + lane) * 4;
+            f32x4 wf[NBT], xq[G];
+#pragma unroll
+            for (int t = 0; t < NBT; ++t) wf[t] = *reinterpret_cast<const f32x4 *>(wp + t * 256);
+#pragma unroll
+            for (int q = 0; q < G; ++q) xq[q] = load_pair_quad(xin[q] + aboff, k2, 16 * kb + 4 * g, vec);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+              for (int t = 0; t < NBT; ++t)
+#pragma unroll
+                for (int q = 0; q < G; ++q) acc[q][t] = mfma4(wf[t][j], xq[q][j], acc[q][t]);
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < G; ++q)
+        if (ok[q]) {
+#pragma unroll
+          for (int t = 0; t < NBT; ++t)
+            store_quad(a.out + mo[q] * a.cout, 16 * (nb0 + t) + 4 * g, a.cout, acc[q][t], a.act);
+        }
+    }
+  }
+}
+
 // a concatenation written out (a program that holds a Conv3DTranspose may feed one to a
 // 1x1x1 conv): each operand a cubic buffer seen through up / crop
 __global__ void concat_view_f32(const float *__restrict__ a, int aD, int aC, int aup, int acrop,
@@ -1114,6 +1250,57 @@ int launch_deconv(fpl_ctx *ctx, DeconvF &a) {
     case 2: deconv2_f32<2, 4><<<grid, 256, 0, ctx->stream>>>(a); break;
     case 3: deconv2_f32<3, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
     default: deconv2_f32<0, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
+  }
+  return 0;
+}
+
+// the instance of down2_f32 that runs cin -> cout: K-blocks per tap pair held in registers
+// (0: the any-cin form) and the N-blocks per pass, which the fragments are padded to
+static void down_form(int cin, int *nkb_reg, int *nbt) {
+  const int nkb = (2 * cin + 15) / 16;
+  *nkb_reg = nkb <= 2 ? nkb : 0;
+  *nbt = nkb <= 2 ? 2 : 4;
+}
+
+// down fragments [ab][kb][nb][lane][j] = W[ab][kk = 16 kb + 4g + j][co = 16 nb + (lane & 15)] *
+// scale[co] with kk = c * cin + ci inside the (a, b) tap pair (the kernel's own memory order:
+// [a][b][c][ci][co]), then the shifts, both padded with zeros to nbp N-blocks
+void pack_down_f32(const float *W, const float *scale, const float *shift, int cin, int cout,
+                   std::vector<float> *out) {
+  int nkb_reg, nbt;
+  down_form(cin, &nkb_reg, &nbt);
+  const int k2 = 2 * cin, nkb = (k2 + 15) / 16;
+  const int nbp = ((cout + 15) / 16 + nbt - 1) / nbt * nbt;
+  out->assign((size_t)4 * nkb * nbp * 256 + (size_t)16 * nbp, 0.f);
+  for (int ab = 0; ab < 4; ++ab)
+    for (int kb = 0; kb < nkb; ++kb)
+      for (int nb = 0; nb < nbp; ++nb)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int co = 16 * nb + (lane & 15), g = lane >> 4;
+          if (co >= cout) continue;
+          for (int j = 0; j < 4; ++j) {
+            const int kk = 16 * kb + 4 * g + j;
+            if (kk >= k2) continue;
+            (*out)[((((size_t)ab * nkb + kb) * nbp + nb) * 64 + lane) * 4 + j] =
+                W[((size_t)ab * k2 + kk) * cout + co] * scale[co];
+          }
+        }
+  float *sh = out->data() + (size_t)4 * nkb * nbp * 256;
+  for (int co = 0; co < cout; ++co) sh[co] = shift[co];
+}
+
+int launch_down(fpl_ctx *ctx, DownF &a) {
+  int nkb_reg, nbt;
+  down_form(a.cin, &nkb_reg, &nbt);
+  // as instantiated below (two voxel groups with two K-blocks per tap pair in registers took 132 VGPRs)
+  const int G = nkb_reg == 2 ? 1 : 2;
+  const int64_t groups = ceil_div64(a.M, 16 * G);
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div64(groups, 4), (int64_t)ctx->n_cu * 8);
+  TimedLaunch tl(ctx, "mfma_down2_f32");
+  switch (nkb_reg) {
+    case 1: down2_f32<1, 2, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
+    case 2: down2_f32<2, 1, 2><<<grid, 256, 0, ctx->stream>>>(a); break;
+    default: down2_f32<0, 2, 4><<<grid, 256, 0, ctx->stream>>>(a); break;
   }
   return 0;
 }
@@ -1264,11 +1451,12 @@ static std::vector<char> concats_written(const fpl_program *prog) {
   return out;
 }
 
-// programs made of voxel GEMMs only (1x1x1 convs and Conv3DTransposes) run on tiles of any
-// extents; everything else is written for cubic tiles
+// programs made of voxel GEMMs only (1x1x1 convs, Conv3DTransposes and strided Conv3D(2)s) run
+// on tiles of any extents; everything else is written for cubic tiles
 bool fpl_mfma_f32_any_dims(const fpl_program *prog) {
   for (auto &op : prog->ops)
-    if (!(op.kind == FPL_OP_DECONV || (op.kind == FPL_OP_CONV && op.k == 1))) return false;
+    if (!(op.kind == FPL_OP_DECONV || op.kind == FPL_OP_DOWN || (op.kind == FPL_OP_CONV && op.k == 1)))
+      return false;
   return true;
 }
 
@@ -1312,6 +1500,7 @@ bool fpl_mfma_f32_supported(const fpl_program *prog) {
       if (op.k == 1 && op.cout > 128) return false;
     }
     if (op.kind == FPL_OP_DECONV && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
+    if (op.kind == FPL_OP_DOWN && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
   }
   return true;
 }
@@ -1345,6 +1534,13 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
       if (op.kind == FPL_OP_DECONV) {
         std::vector<float> f;
         pack_deconv_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
+        st->off[i] = all.size();
+        all.insert(all.end(), f.begin(), f.end());
+        continue;
+      }
+      if (op.kind == FPL_OP_DOWN) {
+        std::vector<float> f;
+        pack_down_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
         st->off[i] = all.size();
         all.insert(all.end(), f.begin(), f.end());
         continue;
@@ -1459,6 +1655,7 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
     if (op.kind == FPL_OP_POOL) { od = a.dim / 2; oc = a.C; }
     if (op.kind == FPL_OP_ADD) { od = a.dim; oc = a.C; }
     if (op.kind == FPL_OP_DECONV) { od = 2 * a.dim; oc = op.cout; }
+    if (op.kind == FPL_OP_DOWN) { od = a.dim / 2; oc = op.cout; }      // sizes as a pool's
     FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
     const int od_conv = od;                       // conv3's own output edge
     const fpl_op &last = fusep >= 0 ? prog->ops[fusep] : (fuse1 >= 0 ? prog->ops[fuse1] : op);
@@ -1467,6 +1664,7 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
     // extents of the result: cubic, but for the voxel GEMMs, which follow their input's
     int oD = od, oH = od, oW = od;
     if (op.kind == FPL_OP_DECONV) { oD = 2 * a.D; oH = 2 * a.H; oW = 2 * a.W; }
+    else if (op.kind == FPL_OP_DOWN) { oD = a.D / 2; oH = a.H / 2; oW = a.W / 2; }
     else if (op.kind == FPL_OP_CONV && op.k == 1) { oD = a.D; oH = a.H; oW = a.W; }
     if (last.dst == prog->out_tensor) {
       dst = out;
@@ -1485,6 +1683,19 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
       c.shift = c.w + (size_t)4 * c.nb2 * ((op.cin + 15) / 16) * 256;
       c.act = op.act; c.out = dst; c.cout = op.cout;
       FPL_TRY(launch_deconv(ctx, c));
+    } else if (op.kind == FPL_OP_DOWN) {
+      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: strided Conv3D of a view", i);
+      FPL_REQUIRE(ctx, oD > 0 && oH > 0 && oW > 0, "op %zu: tile %d is too small for this architecture", i, T);
+      int nkb_reg, nbt;
+      down_form(op.cin, &nkb_reg, &nbt);
+      DownF c;
+      c.in = a.p; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
+      c.OD = oD; c.OH = oH; c.OW = oW; c.M = (int64_t)n * oD * oH * oW;
+      c.nbp = ((op.cout + 15) / 16 + nbt - 1) / nbt * nbt;
+      c.w = st->frags + st->off[i];
+      c.shift = c.w + (size_t)4 * ((2 * op.cin + 15) / 16) * c.nbp * 256;
+      c.act = op.act; c.out = dst; c.cout = op.cout;
+      FPL_TRY(launch_down(ctx, c));
     } else if (op.kind == FPL_OP_ADD) {
       const View b = view[op.src1];
       FPL_REQUIRE(ctx, a.p && b.p && a.up == 1 && b.up == 1 && a.dim == b.dim && a.C == b.C,

@@ -83,6 +83,12 @@ int fpl_infer_shapes(fpl_ctx *ctx, const fpl_program *prog,
         o.d = 2 * a.d; o.h = 2 * a.h; o.w = 2 * a.w;
         o.c = op.cout;
         break;
+      case FPL_OP_DOWN:
+        FPL_REQUIRE(ctx, a.c == op.cin, "op %zu: strided conv cin %d != input channels %d",
+                    i, op.cin, a.c);
+        o.d = a.d / 2; o.h = a.h / 2; o.w = a.w / 2;
+        o.c = op.cout;
+        break;
       case FPL_OP_POOL:
         o.d = a.d / op.p[0]; o.h = a.h / op.p[1]; o.w = a.w / op.p[2];
         break;
@@ -168,6 +174,13 @@ int fpl_forward_generic(fpl_ctx *ctx, fpl_program *prog, const float *in_dev,
       case FPL_OP_DECONV: {
         TimedLaunch tl(ctx, "generic_deconv2_f32");
         deconv2_direct_f32<<<grid1d(n_out), 256, 0, st>>>(
+            buf[op.src0], A + op.w_off, A + op.scale_off, A + op.shift_off, dst, n_out,
+            a.d, a.h, a.w, op.cin, op.cout, op.act);
+        break;
+      }
+      case FPL_OP_DOWN: {
+        TimedLaunch tl(ctx, "generic_down2_f32");
+        down2_direct_f32<<<grid1d(n_out), 256, 0, st>>>(
             buf[op.src0], A + op.w_off, A + op.scale_off, A + op.shift_off, dst, n_out,
             a.d, a.h, a.w, op.cin, op.cout, op.act);
         break;
@@ -267,6 +280,21 @@ int fpl_program_create(fpl_ctx *ctx, const fpl_op *ops, int32_t n_ops,
                   op.cin, op.cout);
       FPL_REQUIRE(ctx, op.act == FPL_ACT_NONE || op.act == FPL_ACT_RELU,
                   "fpl_program_create: op %d Conv3DTranspose activation %d (none or relu)", i, op.act);
+      const int64_t kk = (int64_t)8 * op.cin * op.cout;
+      FPL_REQUIRE(ctx, op.w_off >= 0 && op.w_off + kk <= n_arena && op.scale_off >= 0 &&
+                           op.scale_off + op.cout <= n_arena && op.shift_off >= 0 &&
+                           op.shift_off + op.cout <= n_arena,
+                  "fpl_program_create: op %d weight offsets exceed the arena", i);
+    }
+    if (op.kind == FPL_OP_DOWN) {
+      FPL_REQUIRE(ctx, op.k == 2 && op.p[0] == 2 && op.p[1] == 2 && op.p[2] == 2,
+                  "fpl_program_create: op %d strided Conv3D kernel %d strides (%d,%d,%d) (only "
+                  "kernel 2 with strides 2)", i, op.k, op.p[0], op.p[1], op.p[2]);
+      FPL_REQUIRE(ctx, op.cin > 0 && op.cout > 0 && op.cin <= 256 && op.cout <= 256,
+                  "fpl_program_create: op %d strided Conv3D %d -> %d channels (1 .. 256)", i,
+                  op.cin, op.cout);
+      FPL_REQUIRE(ctx, op.act == FPL_ACT_NONE || op.act == FPL_ACT_RELU,
+                  "fpl_program_create: op %d strided Conv3D activation %d (none or relu)", i, op.act);
       const int64_t kk = (int64_t)8 * op.cin * op.cout;
       FPL_REQUIRE(ctx, op.w_off >= 0 && op.w_off + kk <= n_arena && op.scale_off >= 0 &&
                            op.scale_off + op.cout <= n_arena && op.shift_off >= 0 &&

@@ -100,6 +100,12 @@ bool has_deconv(const fpl_program *prog) {
   return false;
 }
 
+bool has_down(const fpl_program *prog) {
+  for (auto &op : prog->ops)
+    if (op.kind == FPL_OP_DOWN) return true;
+  return false;
+}
+
 // does one of the three builds of conv_mfma.hip run this program at this precision?
 bool h16_executor_takes(const fpl_program *prog, int precision) {
   return fpl_unet_fast_available_bf16(prog, precision) || fpl_unet_fast_available_f16(prog, precision) ||
@@ -115,7 +121,8 @@ bool tiles_mergeable(const fpl_program *prog, const std::vector<TensorShape> &sh
     // (a Conv3DTranspose returns to a finer lattice than the deepest pool's, which the argument
     // below does not cover: declined like an upsampling - DESIGN.md, "Conv3DTranspose")
     if (op.kind == FPL_OP_UP || op.kind == FPL_OP_DECONV) return false;
-    if (op.kind == FPL_OP_POOL) {
+    // (a strided Conv3D(2) halves the lattice exactly as a pool does)
+    if (op.kind == FPL_OP_POOL || op.kind == FPL_OP_DOWN) {
       const TensorShape &t = shp[op.src0];
       if (t.d % op.p[0] || t.h % op.p[1] || t.w % op.p[2]) return false;
     }
@@ -174,8 +181,9 @@ int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
     net_out = (float *)p;
   }
   const bool cubic = in_dims[0] == in_dims[1] && in_dims[1] == in_dims[2];
-  // (a program that holds a Conv3DTranspose and nothing but voxel GEMMs runs on any extents)
-  const bool any_dims = has_deconv(prog) && fpl_mfma_f32_any_dims(prog);
+  // (a program that holds a Conv3DTranspose or a strided Conv3D(2) and nothing but voxel GEMMs runs
+  // on any extents)
+  const bool any_dims = (has_deconv(prog) || has_down(prog)) && fpl_mfma_f32_any_dims(prog);
   if ((cubic || any_dims) && fpl_mfma_f32_supported(prog) && !getenv("FPL_FORCE_PEROP")) {
     set_last_path(ctx, "mfma_f32");
     FPL_TRY(fpl_forward_mfma_f32_dims(ctx, prog, in_dev, n, in_dims, net_out));
@@ -264,6 +272,9 @@ static int infer_volume_impl(fpl_ctx *ctx, fpl_program *prog, const void *src,
   // the fused fast path writes every valid voxel itself: only the border shell
   // needs clearing there; the per-op path stitches tiles into a zeroed volume
   const bool cubic = tile_in[0] == tile_in[1] && tile_in[1] == tile_in[2];
+  FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_down(prog),
+              "fpl_infer_volume: no 16-bit MFMA kernels for the layer Conv3D(filters, 2, strides=2): this network "
+              "runs in fp32 only; use precision f32 (or 'auto')");
   // (a Conv3DTranspose has 16-bit / split-half kernels on the graph executor only: gx_exec.h)
   FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_deconv(prog) || (cubic && h16_executor_takes(prog, precision)),
               "fpl_infer_volume: the 16-bit / split-half graph executor does not take this program's "

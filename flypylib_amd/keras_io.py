@@ -17,7 +17,12 @@ class (file order when a name has none) and assigned to the graph's convolution 
 nodes in creation order; every shape is checked.  A Conv3DTranspose owns kernel / bias too
 (kernel `(2,2,2,Cout,Cin)`, out-channels first) and is numbered in a class of its own
 (`conv3d_transpose_1`): layers whose name says `transpose`, or - a user-named layer - whose
-kernel has the edge 2 no Conv3D of this package has, go to the graph's deconv nodes.
+kernel has the edge 2 no stride-1 Conv3D of this package has, go to the graph's deconv nodes.
+A Conv3D(filters, 2, strides=2) (`LayerGraph.down`) is a Conv3D to Keras: it is written and
+numbered as `conv3d_N` with the other convolutions and, read back under such a name, takes its
+turn among them.  User-named layers with an edge-2 kernel cannot be told apart by name: they are
+dealt, in file order, to the graph's edge-2 nodes (deconv and down) in creation order, and the
+shape check catches a file that does not fit.
 
 Files are read with h5py when it is installed and with the package's own reader
 (`h5min`: the HDF5 subset Keras files use) otherwise; they are written with `h5min`.
@@ -96,25 +101,39 @@ def _creation_order(layers):
 def graph_weights_from_layers(graph, layers):
     """arrays in `graph.get_weights()` order"""
     convs = [(n, it) for n, it in layers if {r for r, _ in it} <= {'kernel', 'bias'}]
-    def is_transpose(layer):
-        # Keras' automatic name says so; a user-named layer is told by its kernel: (2,2,2,Cout,Cin)
-        # can only be a Conv3DTranspose here, the package's Conv3D kernels have edge 1 or 3
+    def edge2(layer):
         kern = [a for r, a in layer[1] if r == 'kernel']
-        return 'transpose' in layer[0].lower() or (len(kern) == 1 and tuple(kern[0].shape[:3]) == (2, 2, 2))
+        return len(kern) == 1 and tuple(kern[0].shape[:3]) == (2, 2, 2)
+    def is_transpose(layer):
+        # Keras' automatic name says so
+        return 'transpose' in layer[0].lower()
+    def is_named_edge2(layer):
+        # a user-named layer with an edge-2 kernel: a Conv3DTranspose or a strided Conv3D, told
+        # by its turn among the graph's edge-2 nodes (Keras' own `conv3d_N` is a convolution)
+        return not is_transpose(layer) and edge2(layer) and not re.match(r'conv3d_\d+$', layer[0])
     deconvs = [l for l in convs if is_transpose(l)]
-    convs = [l for l in convs if not is_transpose(l)]
+    named2 = [l for l in convs if is_named_edge2(l)]
+    convs = [l for l in convs if not is_transpose(l) and not is_named_edge2(l)]
     bns = [(n, it) for n, it in layers if {r for r, _ in it} & {'gamma', 'beta', 'moving_mean'}]
     other = [n for n, it in layers
-             if (n, it) not in convs and (n, it) not in bns and (n, it) not in deconvs]
+             if (n, it) not in convs and (n, it) not in bns and (n, it) not in deconvs
+             and (n, it) not in named2]
     if other:
         raise ValueError('layers with weights this package has no counterpart for: %s' % other)
     convs, bns, deconvs = _creation_order(convs), _creation_order(bns), _creation_order(deconvs)
     out = [None] * len(graph.weights)
-    ci = bi = di = 0
+    ci = bi = di = ei = 0
     for node in graph.nodes:
-        if node.kind not in ('conv', 'bn', 'deconv'):
+        if node.kind not in ('conv', 'bn', 'deconv', 'down'):
             continue
-        pool, idx = {'conv': (convs, ci), 'bn': (bns, bi), 'deconv': (deconvs, di)}[node.kind]
+        took = node.kind
+        if node.kind == 'deconv' and di >= len(deconvs) and ei < len(named2):
+            took = 'named2'
+        elif node.kind == 'down':
+            # its turn among the convolutions, unless the file names its edge-2 layers itself
+            took = 'conv' if ci < len(convs) and edge2(convs[ci]) else 'named2' if ei < len(named2) else 'conv'
+        pool, idx = {'conv': (convs, ci), 'bn': (bns, bi), 'deconv': (deconvs, di),
+                     'named2': (named2, ei)}[took]
         if idx >= len(pool):
             raise ValueError('the file has %d %s layers, the network needs more'
                              % (len(pool), node.kind))
@@ -129,17 +148,20 @@ def graph_weights_from_layers(graph, layers):
                 raise ValueError('%s/%s has shape %s, the network expects %s'
                                  % (name, role, tuple(arr.shape), tuple(want)))
             out[slot] = np.asarray(arr, np.float32)
-        if node.kind == 'conv':
+        if took == 'conv':
             ci += 1
-        elif node.kind == 'deconv':
+        elif took == 'deconv':
             di += 1
+        elif took == 'named2':
+            ei += 1
         else:
             bi += 1
     if ci != len(convs) or bi != len(bns):
         raise ValueError('the file has %d conv / %d BN layers, the network %d / %d'
                          % (len(convs), len(bns), ci, bi))
-    if di != len(deconvs):
-        raise ValueError('the file has %d Conv3DTranspose layers, the network %d' % (len(deconvs), di))
+    if di != len(deconvs) or ei != len(named2):
+        raise ValueError('the file has %d Conv3DTranspose layers, the network %d'
+                         % (len(deconvs) + len(named2), di + ei))
     return out
 
 
@@ -148,7 +170,7 @@ def _trainable_slots(graph):
     (, bias) / gamma, beta - the moving statistics are not trainable"""
     out = []
     for node in graph.nodes:
-        if node.kind in ('conv', 'deconv'):
+        if node.kind in ('conv', 'deconv', 'down'):
             out.extend(node.weight_slots)
         elif node.kind == 'bn':
             out.extend(node.weight_slots[:2])
@@ -223,7 +245,7 @@ def weight_tree(graph):
     """the `save_weights` tree of a graph (h5min.write's input): Keras' automatic layer
     names in creation order, one group per layer of the graph (weightless ones included,
     as Keras lists them)"""
-    roles = {'conv': ['kernel', 'bias'], 'deconv': ['kernel', 'bias'],
+    roles = {'conv': ['kernel', 'bias'], 'deconv': ['kernel', 'bias'], 'down': ['kernel', 'bias'],
              'bn': ['gamma', 'beta', 'moving_mean', 'moving_variance']}
     names = _layer_names(graph)
     layer_names, groups = [], {}
@@ -249,7 +271,8 @@ _KERAS_CLASS = {'conv': ('Conv3D', 'conv3d'), 'bn': ('BatchNormalization', 'batc
                 'drop': ('Dropout', 'dropout'), 'up': ('UpSampling3D', 'up_sampling3d'),
                 'crop': ('Cropping3D', 'cropping3d'), 'concat': ('Concatenate', 'concatenate'),
                 'add': ('Add', 'add'), 'input': ('InputLayer', 'input'),
-                'deconv': ('Conv3DTranspose', 'conv3d_transpose')}
+                'deconv': ('Conv3DTranspose', 'conv3d_transpose'),
+                'down': ('Conv3D', 'conv3d')}
 
 
 def _layer_names(graph):
@@ -282,9 +305,10 @@ def model_config(graph):
             spatial = list(graph.in_sz) if graph.in_sz is not None else [None, None, None]
             cfg = {'batch_input_shape': [None] + spatial + [1], 'dtype': 'float32',
                    'sparse': False, 'name': name}
-        elif node.kind == 'conv':
+        elif node.kind in ('conv', 'down'):
             k = int(a['k'])
-            cfg.update(filters=int(node.channels), kernel_size=[k, k, k], strides=[1, 1, 1],
+            st = 2 if node.kind == 'down' else 1
+            cfg.update(filters=int(node.channels), kernel_size=[k, k, k], strides=[st, st, st],
                        padding='valid', data_format='channels_last', dilation_rate=[1, 1, 1],
                        activation=a['activation'] or 'linear', use_bias=bool(a['use_bias']),
                        kernel_initializer=glorot, bias_initializer=zeros,

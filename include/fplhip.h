@@ -38,7 +38,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define FPL_ABI_VERSION 10
+#define FPL_ABI_VERSION 11
 
 typedef struct fpl_ctx fpl_ctx;
 typedef struct fpl_program fpl_program;
@@ -92,7 +92,14 @@ enum fpl_op_kind {
    * 128 -> 64 channels, on a materialised tensor, not under a pool) and refuse the program
    * with the layer named otherwise; fp32 runs it always.
    * New in ABI 10 - a version 9 library does not know the kind, hence the bump */
-  FPL_OP_DECONV = 6
+  FPL_OP_DECONV = 6,
+  /* Conv3D(cout, 2, strides=2, 'valid'), the learned 2x down-convolution (k = 2, p0..p2 = 2):
+   * y[i][j][k][co] = act(shift[co] + scale[co] * sum_{a,b,c,ci} x[2i+a][2j+b][2k+c][ci] *
+   * W[a][b][c][ci][co]); kernel [8*cin][cout] (Keras memory order); an odd axis drops its
+   * last plane, as MaxPooling3D(2) does.  fp32 executors only: the 16-bit / split precisions
+   * refuse a program that holds it.
+   * New in ABI 11 - a version 10 library does not know the kind, hence the bump */
+  FPL_OP_DOWN = 7
 };
 enum fpl_act { FPL_ACT_NONE = 0, FPL_ACT_RELU = 1, FPL_ACT_SIGMOID = 2 };
 
@@ -100,13 +107,13 @@ typedef struct fpl_op {
   int32_t kind;      /* fpl_op_kind                                          */
   int32_t src0, src1;/* tensor ids (0 = network input); src1 = -1 if unused  */
   int32_t dst;       /* tensor id produced                                   */
-  int32_t k;         /* conv kernel edge (1 or 3); deconv: 2                 */
+  int32_t k;         /* conv kernel edge (1 or 3); deconv, down: 2           */
   int32_t cin, cout; /* channels in / out                                    */
   int32_t act;       /* fpl_act                                              */
   int64_t w_off;     /* offsets (floats) into the weight arena:              */
   int64_t scale_off; /*   kernel [k^3*cin][cout] (Keras memory order),       */
   int64_t shift_off; /*   scale[cout], shift[cout]                           */
-  int32_t p[6];      /* pool/up factors, crop pairs or deconv strides        */
+  int32_t p[6];      /* pool/up factors, crop pairs, deconv / down strides   */
 } fpl_op;
 
 /* ---- context -------------------------------------------------------------- */
@@ -274,14 +281,19 @@ enum fpl_layer_kind {
    * for convolutions below.  Its gradients are sums in a fixed order (no float atomics), and
    * in a network that holds it so are the convolutions' weight gradients: equal inputs give
    * equal bits.  New in ABI 10 */
-  FPL_L_DECONV = 9
+  FPL_L_DECONV = 9,
+  /* Conv3D(cout, 2, strides=2, 'valid') (FPL_OP_DOWN): k = 2, p0..p2 = 2, kernel
+   * [8*cin][cout] at w_off[0], bias at w_off[1]; act none or relu, under the rule stated for
+   * convolutions below.  Its own gradients are sums in a fixed order (no float atomics); it
+   * does not change which kernels the other layers run.  New in ABI 11 */
+  FPL_L_DOWN = 10
 };
 typedef struct fpl_layer {
   int32_t kind;        /* fpl_layer_kind                                       */
   int32_t src0, src1;  /* tensor ids (0 = network input)                       */
   int32_t dst;
-  int32_t k, cin, cout;/* conv / deconv                                        */
-  int32_t use_bias;    /* conv / deconv                                        */
+  int32_t k, cin, cout;/* conv / deconv / down                                 */
+  int32_t use_bias;    /* conv / deconv / down                                 */
   int32_t act;         /* conv / deconv activation (fpl_act): relu on any conv but the
                         * head (applied in the conv epilogue, its gradient masked
                         * in place in the backward pass; not in front of a BN),

@@ -85,6 +85,13 @@
             substack with 3 000 ground-truth points and 3 000 detections (half of them beside a
             ground-truth point), one warm-up and then the median, min and max of 5: construction,
             scores, gallery('fn'), gallery('fp'); written to profiles/errors.json
+  down      Conv3D(filters, 2, strides=2) (LayerGraph.down), all in one process, one warm-up and
+            then the median, min and max of 5: the example network of tests/down_cases.py
+            (tiny_vnet) inferring a resident 390^3 volume at tile 102 (pitch 96) on mfma_f32 with
+            the per-kernel table; its training step at 8 x 62^3 patches with the per-kernel table;
+            and the down kernel alone (HIP events) at 16 -> 32, 48 -> 64 and 96 -> 128 channels
+            beside a device-to-device copy of the bytes it reads and MaxPooling3D(2) of the same
+            input; no gate; written to profiles/down.json
 These are NOT the driver's bench line (bench.py); they document where the other
 rows of SURVEY section 8 stand.
 """
@@ -1195,6 +1202,115 @@ def deconv_gx_bench(ctx, torch, vol, reps, stats, table, alone):
     return res
 
 
+def down_bench(ctx, torch, vol=390, reps=5):
+    """the example network with a Conv3D(filters, 2, strides=2) end to end, and the kernel alone
+    beside a device copy of the bytes it reads and beside MaxPooling3D(2) of the same input"""
+    from flypylib_amd import FplNetwork, _capi
+    from flypylib_amd.program import LayerGraph
+    from tests import down_cases as dn
+
+    def stats(v):
+        return {'median': round(float(np.median(v)), 4), 'min': round(float(min(v)), 4),
+                'max': round(float(max(v)), 4)}
+
+    def table():
+        return {k: {'ms': round(v['ms'], 4), 'launches': int(v['launches'])}
+                for k, v in sorted(ctx.timing_get().items(), key=lambda kv: -kv[1]['ms'])}
+    out = {'reps': reps, 'note': 'one warm-up, then median / min / max of %d; resident source and '
+                                 'destination; no gate: the path did not exist before' % reps}
+    # ---- tiny_vnet over a volume -------------------------------------------------------------
+    net = FplNetwork(lambda in_sz=None: dn.tiny_vnet_random((102,) * 3 if in_sz is None else in_sz))
+    net._set_infer()
+    src = torch.from_numpy(np.random.default_rng(0).standard_normal((vol,) * 3).astype(np.float32)).to('cuda:0')
+    dst = torch.empty((vol,) * 3, dtype=torch.float32, device='cuda:0')
+    prog = net.infer_network.program
+    kw = dict(precision=_capi.PREC_F32, dst=dst, dims=(vol,) * 3)
+    ms = []
+    for r in range(reps + 1):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        prog.infer_volume(src, net.infer_sz, net.rf_offset, **kw)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    path = ctx.last_path()
+    ctx.timing(True); ctx.timing_reset()
+    prog.infer_volume(src, net.infer_sz, net.rf_offset, **kw)
+    kern = table()
+    ctx.timing(False)
+    out['tiny_vnet_infer'] = {'volume': [vol] * 3, 'tile_in': 102, 'pitch': 96, 'executor': path,
+                              'ms': stats(ms[1:]), 'runs_ms': [round(x, 3) for x in ms[1:]],
+                              'mvox_s': round(vol ** 3 / np.median(ms[1:]) / 1e3, 1), 'kernels_one_pass': kern}
+    print('infer', json.dumps(out['tiny_vnet_infer']['ms']), flush=True)
+    del src, dst
+    # ---- its training step -------------------------------------------------------------------
+    batch, patch = 8, 62
+    g = dn.tiny_vnet((patch,) * 3)[0]
+    rng = np.random.default_rng(1)
+    x = torch.from_numpy(rng.standard_normal((batch,) + (patch,) * 3 + (1,)).astype(np.float32)).to('cuda:0')
+    y = torch.from_numpy((rng.random((batch,) + (patch - 6,) * 3 + (1,)) < 0.3).astype(np.uint8)).to('cuda:0')
+    tr = _capi.Trainer(ctx, g)
+    ms = []
+    for r in range(reps + 1):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        tr.step(x, y, seed=r); tr.apply(1.0)
+        ctx.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    ctx.timing(True); ctx.timing_reset()
+    tr.step(x, y, seed=0); tr.apply(1.0)
+    ctx.synchronize()
+    kern = table()
+    ctx.timing(False)
+    tr.close()
+    out['tiny_vnet_train_step'] = {
+        'batch': batch, 'patch': patch, 'ms': stats(ms[1:]), 'runs_ms': [round(v, 3) for v in ms[1:]],
+        'note': 'the network holds a Conv3DTranspose too: fixed-order weight gradients for every convolution',
+        'kernels_one_step': kern}
+    print('train', json.dumps(out['tiny_vnet_train_step']['ms']), flush=True)
+    del x, y
+    # ---- the kernel alone ----------------------------------------------------------------------
+    def kernel_ms(graph, xin, yshape, name):
+        p = _capi.Program(ctx, graph)
+        yout = torch.empty(yshape, dtype=torch.float32, device='cuda:0')
+        v = []
+        for r in range(reps + 1):
+            ctx.timing(True); ctx.timing_reset()
+            p.forward_device(xin, out=yout)
+            t = ctx.timing_get()
+            ctx.timing(False)
+            v.append(t[name]['ms'])
+        p.close()
+        return v[1:]
+    alone = {}
+    for cin, cout, n, edge in ((16, 32, 8, 96), (48, 64, 2, 96), (96, 128, 2, 80)):
+        xin = torch.randn((n,) + (edge,) * 3, device='cuda:0')
+        g, _ = dn.down_graph(cin, cout, 1, 1, 1, (edge,) * 3)
+        k_ms = kernel_ms(g, xin, (n,) + (edge // 2,) * 3 + (cout,), 'mfma_down2_f32')
+        pg = LayerGraph((edge,) * 3)
+        pg.finish(pg.pool(pg.conv(pg.input(), cin, 1, use_bias=True)))
+        p_ms = kernel_ms(pg, xin, (n,) + (edge // 2,) * 3 + (cin,), 'mfma_pool_f32')
+        rd = n * edge ** 3 * cin * 4
+        wr = n * (edge // 2) ** 3 * cout * 4
+        a_, b_ = torch.empty(rd // 4, device='cuda:0'), torch.empty(rd // 4, device='cuda:0')
+        c_ms = []
+        for r in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            b_.copy_(a_)
+            e1.record(); e1.synchronize()
+            c_ms.append(e0.elapsed_time(e1))
+        del a_, b_, xin
+        km, pm, cm = float(np.median(k_ms)), float(np.median(p_ms)), float(np.median(c_ms[1:]))
+        key = '%dto%d_%dx%d' % (cin, cout, n, edge)
+        alone[key] = {
+            'output_voxels': n * (edge // 2) ** 3, 'bytes_read': rd, 'bytes_written': wr,
+            'kernel_ms': stats(k_ms), 'load_gb_s': round(rd / km / 1e6, 1),
+            'd2d_copy_of_the_bytes_read_ms': stats(c_ms[1:]), 'kernel_over_copy': round(km / cm, 3),
+            'maxpool_same_input_ms': stats(p_ms), 'kernel_over_maxpool': round(km / pm, 3)}
+        print(key, json.dumps(alone[key]), flush=True)
+    out['down_kernel_alone'] = alone
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
@@ -1438,6 +1554,11 @@ def main():
         res['deconv'] = deconv_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'deconv.json')
+
+    if 'down' in what:
+        res['down'] = down_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'down.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
