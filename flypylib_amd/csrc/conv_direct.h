@@ -1,4 +1,4 @@
-// Direct fp32 conv / transposed-conv / strided-conv kernels shared by the per-op inference executor (generic.hip)
+// Direct fp32 conv / transposed-conv / strided-conv / dilated-conv kernels shared by the per-op inference executor (generic.hip)
 // and the training engine (train.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,6 +95,31 @@ static __global__ __launch_bounds__(256) void down2_direct_f32(
   for (int tap = 0; tap < 8; ++tap) {
     const float *xp = x + ((((t * D + 2 * oz + (tap >> 2)) * H + 2 * oy + ((tap >> 1) & 1)) * (int64_t)W +
                             2 * ox + (tap & 1)) * cin);
+    const float *wp = w + (int64_t)tap * cin * cout + co;
+    for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[(int64_t)ci * cout], acc);
+  }
+  y[i] = apply_act(fmaf(acc, scale[co], shift[co]), act);
+}
+
+// Direct Conv3D(cout, 3, dilation_rate=2, 'valid'): the readable restatement of FPL_OP_DILATED.
+// One thread = one output element, 27 taps two voxels apart of cin products each in
+// (a, b, c, ci) order.  x (n, D, H, W, cin), w [27][cin][cout], y (n, D-4, H-4, W-4, cout).
+static __global__ __launch_bounds__(256) void atrous3_direct_f32(
+    const float *__restrict__ x, const float *__restrict__ w,
+    const float *__restrict__ scale, const float *__restrict__ shift,
+    float *__restrict__ y, int64_t n_out, int D, int H, int W, int cin, int cout, int act) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  const int od = D - 4, oh = H - 4, ow = W - 4;
+  int64_t t = i;
+  const int co = (int)(t % cout); t /= cout;
+  const int ox = (int)(t % ow); t /= ow;
+  const int oy = (int)(t % oh); t /= oh;
+  const int oz = (int)(t % od); t /= od;
+  float acc = 0.f;
+  for (int tap = 0; tap < 27; ++tap) {
+    const float *xp = x + ((((t * D + oz + 2 * (tap / 9)) * H + oy + 2 * ((tap / 3) % 3)) * (int64_t)W +
+                            ox + 2 * (tap % 3)) * cin);
     const float *wp = w + (int64_t)tap * cin * cout + co;
     for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[(int64_t)ci * cout], acc);
   }

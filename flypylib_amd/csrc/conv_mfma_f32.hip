@@ -367,6 +367,145 @@ __global__ __launch_bounds__(256, 2) void conv3_f32(Conv3F a) {
   }
 }
 
+// ---- Conv3D(cout, 3, dilation_rate 2, 'valid') as eight sub-lattice 3x3x3 convolutions ----
+// y[m] = sum_t x[m + 2t] W[t] only ever joins voxels of one parity class: with m = 2 s + q
+// (q in {0,1}^3) it reads x[2 (s + t) + q], so on the sub-lattice x_q[s] = x[2 s + q] it is the
+// PLAIN valid 3x3x3 convolution y_q[s] = sum_t x_q[s + t] W[t].  The kernel is conv3_f32's tile
+// scheme on that sub-lattice - 6 x 6 x 18 voxels of 16 channels at 96 B pitch (62208 B of LDS,
+// two workgroups per CU), 4 x 4 x 16 outputs, one z plane per wave, the weight fragments of
+// pack_conv3_f32 three taps ahead in registers, K order (channel chunk, tap, channel) - with a
+// voxel step of 2 and the parity origin q in the loader and in the store.  A voxel's channel
+// chunk stays one contiguous 64-B piece, so loads and stores keep conv3_f32's width.  One launch
+// runs the eight classes: blockIdx.x = 8 * x block + class; a class has ceil((O - q) / 2)
+// outputs per axis and the blocks beyond its ragged extent leave at once.  The sum of a voxel
+// does not depend on its place in a tile, a class or a block: super-tiles give equal bits.
+struct AtrousF {
+  const float *in;       // (n, D, H, W, C) f32, materialised
+  int D, H, W, C;
+  int ncc;               // channel chunks of 16
+  const float *w;        // fragments [cc][tap][mb][lane][4] (pack_conv3_f32)
+  const float *shift;
+  int act;               // fpl_act
+  float *out;            // (n, D - 4, H - 4, W - 4, opitch)
+  int cout, opitch;      // channels of this launch (<= 16 * MB) / of the tensor
+  int zblocks;           // blocks per class along z
+};
+
+template <int MB>
+__global__ __launch_bounds__(256, 2) void atrous3_f32(AtrousF a) {
+  constexpr int PIECES = TZ * TY * TX * 4;          // 4 x 16 B per voxel (16 ch)
+  constexpr int NT = (PIECES + 255) / 256;
+  unsigned char *tile = smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int cls = blockIdx.x & 7;
+  const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;      // the class's origin
+  // sub-lattice coordinates from here on: voxel s of the class is voxel 2 s + p of the tensor
+  const int x0 = (blockIdx.x >> 3) * 16, y0 = blockIdx.y * 4;
+  const int n = blockIdx.z / a.zblocks, z0 = (blockIdx.z % a.zblocks) * 4;
+  const int OD = a.D - 4, OH = a.H - 4, OW = a.W - 4;
+  const int SD = (OD - pz + 1) >> 1, SH = (OH - py + 1) >> 1, SW = (OW - px + 1) >> 1;
+  if (z0 >= SD || y0 >= SH || x0 >= SW) return;      // the whole workgroup: no barrier is skipped
+  const unsigned vbase = (unsigned)(((wave * TY) * TX + c) * PITCH + g * 16);
+  f32x4 acc[4][MB];
+#pragma unroll
+  for (int b = 0; b < MB; ++b) {
+    f32x4 sh;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int co = 16 * b + 4 * g + r;
+      sh[r] = co < a.cout ? a.shift[co] : 0.f;
+    }
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) acc[sub][b] = sh;
+  }
+  const unsigned total_steps = (unsigned)a.ncc * KB;     // (fragment offsets fit 32 bits: <= 12 * 27 * 4 KiB)
+  const unsigned char *wl = reinterpret_cast<const unsigned char *>(a.w) + lane * 16;
+  f32x4 wq[WQF][MB];
+#pragma unroll
+  for (int d = 0; d < WQF; ++d)
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+      wq[d][b] = *reinterpret_cast<const f32x4 *>(wl + (size_t)(d * MB + b) * 1024);
+
+  for (int cc = 0; cc < a.ncc; ++cc) {
+    __syncthreads();
+    constexpr int NB = 8;
+#pragma unroll 1
+    for (int j0 = 0; j0 < NT; j0 += NB) {
+      u32x4 nt[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        int p = tid + 256 * (j0 + j);
+        p = p < PIECES ? p : PIECES - 1;
+        const int vox = p >> 2, pc = p & 3;
+        int z = 2 * (z0 + vox / (TY * TX)) + pz, y = 2 * (y0 + (vox / TX) % TY) + py,
+            x = 2 * (x0 + vox % TX) + px;
+        const bool ok = z < a.D && y < a.H && x < a.W;
+        z = ok ? z : 0; y = ok ? y : 0; x = ok ? x : 0;
+        const int ch = 16 * cc + pc * 4;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        const float *gp = a.in + ((((int64_t)n * a.D + z) * a.H + y) * a.W + x) * a.C + ch;
+        if (ok) {
+          if (ch + 3 < a.C && (a.C & 3) == 0) {
+            v = *reinterpret_cast<const u32x4 *>(gp);
+          } else {                               // ragged channel tail (C = 1, ...)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (ch + q < a.C) v[q] = __float_as_uint(gp[q]);
+          }
+        }
+        nt[j] = v;
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        int p = tid + 256 * (j0 + j);
+        p = p < PIECES ? p : PIECES - 1;
+        *reinterpret_cast<u32x4 *>(tile + (size_t)(p >> 2) * PITCH + (p & 3) * 16) = nt[j];
+      }
+    }
+    __syncthreads();
+    const unsigned gs0 = (unsigned)cc * KB;
+    // a z plane past the class's extent (ragged last block): nothing to multiply
+    if (z0 + wave >= SD) continue;
+#pragma unroll
+    for (int tap = 0; tap < KB; ++tap) {
+      const unsigned toff = (unsigned)((((tap / 9) * TY + (tap / 3) % 3) * TX + tap % 3) * PITCH);
+      f32x4 bf[4];
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub)
+        bf[sub] = *reinterpret_cast<const f32x4 *>(tile + vbase + toff + sub * TX * PITCH);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+          for (int b = 0; b < MB; ++b)
+            acc[sub][b] = mfma4(wq[tap % WQF][b][j], bf[sub][j], acc[sub][b]);
+      __builtin_amdgcn_s_setprio(0);
+      {
+        unsigned nxt = gs0 + tap + WQF;
+        nxt = nxt < total_steps ? nxt : 0u;            // past the end: a harmless reload
+#pragma unroll
+        for (int b = 0; b < MB; ++b)
+          wq[tap % WQF][b] = *reinterpret_cast<const f32x4 *>(wl + (nxt * MB + b) * 1024u);
+      }
+    }
+  }
+  const int sz = z0 + wave, sx = x0 + c;
+#pragma unroll
+  for (int sub = 0; sub < 4; ++sub) {
+    const int sy = y0 + sub;
+    if (sz < SD && sy < SH && sx < SW) {
+      float *dst = a.out + ((((int64_t)n * OD + 2 * sz + pz) * OH + 2 * sy + py) * OW + 2 * sx + px) * a.opitch;
+#pragma unroll
+      for (int b = 0; b < MB; ++b)
+        store_quad(dst, 16 * b + 4 * g, a.cout, acc[sub][b], a.act);
+    }
+  }
+}
+
 // ---- 1x1x1 conv as a voxel GEMM (fp32) ----------------------------------------------
 // ---- the pooled-gradient view (FplPoolGrad, fast_paths.h) on the device ----------------
 // unsigned division by a run-time constant: q = (t + ((n - t) >> s1)) >> s2, t = umulhi(n, m)
@@ -1370,6 +1509,26 @@ int launch3(fpl_ctx *ctx, Conv3F &a, int n) {
   return 0;
 }
 
+// the eight parity classes of a dilated convolution in one launch: the grid is sized for class
+// (0,0,0), the largest
+template <int MB>
+int launch_atrous(fpl_ctx *ctx, AtrousF &a, int n) {
+  constexpr int SMEM = TILE_BYTES;
+  static bool attr_set[FPL_MAX_DEVICES] = {false};
+  if (!attr_set[ctx->device % FPL_MAX_DEVICES]) {
+    FPL_HIP(ctx, hipFuncSetAttribute((const void *)atrous3_f32<MB>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
+    attr_set[ctx->device % FPL_MAX_DEVICES] = true;
+  }
+  const int OD = a.D - 4, OH = a.H - 4, OW = a.W - 4;
+  a.zblocks = (int)ceil_div64((OD + 1) / 2, 4);
+  dim3 grid((unsigned)(8 * ceil_div64((OW + 1) / 2, 16)), (unsigned)ceil_div64((OH + 1) / 2, 4),
+            (unsigned)(n * a.zblocks));
+  TimedLaunch tl(ctx, "mfma_atrous3_f32");
+  atrous3_f32<MB><<<grid, 256, SMEM, ctx->stream>>>(a);
+  return 0;
+}
+
 // conv3 + chained conv1 (+ pool): the (MB, MB1) pairs the reference's architectures need
 template <int MB, int MB1, bool POOL>
 int launch3_fused(fpl_ctx *ctx, Conv3F &a, int n) {
@@ -1451,11 +1610,13 @@ static std::vector<char> concats_written(const fpl_program *prog) {
   return out;
 }
 
-// programs made of voxel GEMMs only (1x1x1 convs, Conv3DTransposes and strided Conv3D(2)s) run
-// on tiles of any extents; everything else is written for cubic tiles
+// programs made of voxel GEMMs (1x1x1 convs, Conv3DTransposes and strided Conv3D(2)s) and dilated
+// Conv3Ds, whose kernel takes three extents, run on tiles of any extents; everything else is
+// written for cubic tiles
 bool fpl_mfma_f32_any_dims(const fpl_program *prog) {
   for (auto &op : prog->ops)
-    if (!(op.kind == FPL_OP_DECONV || op.kind == FPL_OP_DOWN || (op.kind == FPL_OP_CONV && op.k == 1)))
+    if (!(op.kind == FPL_OP_DECONV || op.kind == FPL_OP_DOWN || op.kind == FPL_OP_DILATED ||
+          (op.kind == FPL_OP_CONV && op.k == 1)))
       return false;
   return true;
 }
@@ -1501,6 +1662,8 @@ bool fpl_mfma_f32_supported(const fpl_program *prog) {
     }
     if (op.kind == FPL_OP_DECONV && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
     if (op.kind == FPL_OP_DOWN && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
+    // (the widths of the plain 3x3x3: 12 channel chunks, slices of 64 outputs)
+    if (op.kind == FPL_OP_DILATED && (op.k != 3 || op.cout > 256 || op.cin > 12 * 16)) return false;
   }
   return true;
 }
@@ -1541,6 +1704,19 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
       if (op.kind == FPL_OP_DOWN) {
         std::vector<float> f;
         pack_down_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
+        st->off[i] = all.size();
+        all.insert(all.end(), f.begin(), f.end());
+        continue;
+      }
+      if (op.kind == FPL_OP_DILATED) {
+        // the plain 3x3x3's fragments: 64 output channels per launch, slices back to back
+        std::vector<float> f;
+        for (int c0 = 0; c0 < op.cout; c0 += 64) {
+          std::vector<float> fs;
+          pack_conv3_f32(A + op.w_off, A + op.scale_off, op.cin, op.cout,
+                         (std::min(64, op.cout - c0) + 15) / 16, &fs, c0);
+          f.insert(f.end(), fs.begin(), fs.end());
+        }
         st->off[i] = all.size();
         all.insert(all.end(), f.begin(), f.end());
         continue;
@@ -1656,6 +1832,7 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
     if (op.kind == FPL_OP_ADD) { od = a.dim; oc = a.C; }
     if (op.kind == FPL_OP_DECONV) { od = 2 * a.dim; oc = op.cout; }
     if (op.kind == FPL_OP_DOWN) { od = a.dim / 2; oc = op.cout; }      // sizes as a pool's
+    if (op.kind == FPL_OP_DILATED) { od = a.dim - 4; oc = op.cout; }
     FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
     const int od_conv = od;                       // conv3's own output edge
     const fpl_op &last = fusep >= 0 ? prog->ops[fusep] : (fuse1 >= 0 ? prog->ops[fuse1] : op);
@@ -1665,7 +1842,9 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
     int oD = od, oH = od, oW = od;
     if (op.kind == FPL_OP_DECONV) { oD = 2 * a.D; oH = 2 * a.H; oW = 2 * a.W; }
     else if (op.kind == FPL_OP_DOWN) { oD = a.D / 2; oH = a.H / 2; oW = a.W / 2; }
+    else if (op.kind == FPL_OP_DILATED) { oD = a.D - 4; oH = a.H - 4; oW = a.W - 4; }
     else if (op.kind == FPL_OP_CONV && op.k == 1) { oD = a.D; oH = a.H; oW = a.W; }
+    FPL_REQUIRE(ctx, oD > 0 && oH > 0 && oW > 0, "op %zu: tile %d is too small for this architecture", i, T);
     if (last.dst == prog->out_tensor) {
       dst = out;
     } else {
@@ -1696,6 +1875,24 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
       c.shift = c.w + (size_t)4 * ((2 * op.cin + 15) / 16) * c.nbp * 256;
       c.act = op.act; c.out = dst; c.cout = op.cout;
       FPL_TRY(launch_down(ctx, c));
+    } else if (op.kind == FPL_OP_DILATED) {
+      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: dilated Conv3D of a view", i);
+      AtrousF c;
+      c.in = a.p; c.D = a.D; c.H = a.H; c.W = a.W; c.C = a.C; c.ncc = (a.C + 15) / 16;
+      c.act = op.act; c.opitch = op.cout;                  // (the output extents are the input's - 4)
+      size_t woff = st->off[i];
+      for (int c0 = 0; c0 < op.cout; c0 += 64) {      // 64 output channels per launch
+        const int cs = std::min(64, op.cout - c0), mb = (cs + 15) / 16;
+        c.w = st->frags + woff; c.shift = prog->arena_dev + op.shift_off + c0;
+        c.out = dst + c0; c.cout = cs;
+        woff += (size_t)c.ncc * 27 * mb * 256;
+        switch (mb) {
+          case 1: FPL_TRY(launch_atrous<1>(ctx, c, n)); break;
+          case 2: FPL_TRY(launch_atrous<2>(ctx, c, n)); break;
+          case 3: FPL_TRY(launch_atrous<3>(ctx, c, n)); break;
+          case 4: FPL_TRY(launch_atrous<4>(ctx, c, n)); break;
+        }
+      }
     } else if (op.kind == FPL_OP_ADD) {
       const View b = view[op.src1];
       FPL_REQUIRE(ctx, a.p && b.p && a.up == 1 && b.up == 1 && a.dim == b.dim && a.C == b.C,

@@ -89,8 +89,8 @@ FPL_DECLARE_H16_PATHS(f16s)
 bool fpl_mfma_f32_supported(const fpl_program *prog);
 int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T,
                          float *out);
-// the same on (n, dims) tiles of any extents, for programs of voxel GEMMs only (1x1x1 convs,
-// Conv3DTransposes: fpl_mfma_f32_any_dims)
+// the same on (n, dims) tiles of any extents, for programs of voxel GEMMs (1x1x1 convs,
+// Conv3DTransposes, strided Conv3D(2)s) and dilated Conv3Ds only: fpl_mfma_f32_any_dims
 bool fpl_mfma_f32_any_dims(const fpl_program *prog);
 int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, int n,
                               const int32_t dims[3], float *out);

@@ -89,6 +89,12 @@ int fpl_infer_shapes(fpl_ctx *ctx, const fpl_program *prog,
         o.d = a.d / 2; o.h = a.h / 2; o.w = a.w / 2;
         o.c = op.cout;
         break;
+      case FPL_OP_DILATED:
+        FPL_REQUIRE(ctx, a.c == op.cin, "op %zu: dilated conv cin %d != input channels %d",
+                    i, op.cin, a.c);
+        o.d = a.d - 4; o.h = a.h - 4; o.w = a.w - 4;
+        o.c = op.cout;
+        break;
       case FPL_OP_POOL:
         o.d = a.d / op.p[0]; o.h = a.h / op.p[1]; o.w = a.w / op.p[2];
         break;
@@ -181,6 +187,13 @@ int fpl_forward_generic(fpl_ctx *ctx, fpl_program *prog, const float *in_dev,
       case FPL_OP_DOWN: {
         TimedLaunch tl(ctx, "generic_down2_f32");
         down2_direct_f32<<<grid1d(n_out), 256, 0, st>>>(
+            buf[op.src0], A + op.w_off, A + op.scale_off, A + op.shift_off, dst, n_out,
+            a.d, a.h, a.w, op.cin, op.cout, op.act);
+        break;
+      }
+      case FPL_OP_DILATED: {
+        TimedLaunch tl(ctx, "generic_atrous3_f32");
+        atrous3_direct_f32<<<grid1d(n_out), 256, 0, st>>>(
             buf[op.src0], A + op.w_off, A + op.scale_off, A + op.shift_off, dst, n_out,
             a.d, a.h, a.w, op.cin, op.cout, op.act);
         break;
@@ -296,6 +309,21 @@ int fpl_program_create(fpl_ctx *ctx, const fpl_op *ops, int32_t n_ops,
       FPL_REQUIRE(ctx, op.act == FPL_ACT_NONE || op.act == FPL_ACT_RELU,
                   "fpl_program_create: op %d strided Conv3D activation %d (none or relu)", i, op.act);
       const int64_t kk = (int64_t)8 * op.cin * op.cout;
+      FPL_REQUIRE(ctx, op.w_off >= 0 && op.w_off + kk <= n_arena && op.scale_off >= 0 &&
+                           op.scale_off + op.cout <= n_arena && op.shift_off >= 0 &&
+                           op.shift_off + op.cout <= n_arena,
+                  "fpl_program_create: op %d weight offsets exceed the arena", i);
+    }
+    if (op.kind == FPL_OP_DILATED) {
+      FPL_REQUIRE(ctx, op.k == 3 && op.p[0] == 2 && op.p[1] == 2 && op.p[2] == 2,
+                  "fpl_program_create: op %d dilated Conv3D kernel %d dilation (%d,%d,%d) (only "
+                  "kernel 3 with dilation_rate 2)", i, op.k, op.p[0], op.p[1], op.p[2]);
+      FPL_REQUIRE(ctx, op.cin > 0 && op.cout > 0 && op.cin <= 256 && op.cout <= 256,
+                  "fpl_program_create: op %d dilated Conv3D %d -> %d channels (1 .. 256)", i,
+                  op.cin, op.cout);
+      FPL_REQUIRE(ctx, op.act == FPL_ACT_NONE || op.act == FPL_ACT_RELU,
+                  "fpl_program_create: op %d dilated Conv3D activation %d (none or relu)", i, op.act);
+      const int64_t kk = (int64_t)27 * op.cin * op.cout;
       FPL_REQUIRE(ctx, op.w_off >= 0 && op.w_off + kk <= n_arena && op.scale_off >= 0 &&
                            op.scale_off + op.cout <= n_arena && op.shift_off >= 0 &&
                            op.shift_off + op.cout <= n_arena,

@@ -106,6 +106,12 @@ bool has_down(const fpl_program *prog) {
   return false;
 }
 
+bool has_dilated(const fpl_program *prog) {
+  for (auto &op : prog->ops)
+    if (op.kind == FPL_OP_DILATED) return true;
+  return false;
+}
+
 // does one of the three builds of conv_mfma.hip run this program at this precision?
 bool h16_executor_takes(const fpl_program *prog, int precision) {
   return fpl_unet_fast_available_bf16(prog, precision) || fpl_unet_fast_available_f16(prog, precision) ||
@@ -121,6 +127,8 @@ bool tiles_mergeable(const fpl_program *prog, const std::vector<TensorShape> &sh
     // (a Conv3DTranspose returns to a finer lattice than the deepest pool's, which the argument
     // below does not cover: declined like an upsampling - DESIGN.md, "Conv3DTranspose")
     if (op.kind == FPL_OP_UP || op.kind == FPL_OP_DECONV) return false;
+    // (a dilated Conv3D is a valid convolution at stride 1: nothing to check, and its kernel's sum
+    // for a voxel does not depend on the voxel's place in the tile - DESIGN.md section 22)
     // (a strided Conv3D(2) halves the lattice exactly as a pool does)
     if (op.kind == FPL_OP_POOL || op.kind == FPL_OP_DOWN) {
       const TensorShape &t = shp[op.src0];
@@ -181,9 +189,9 @@ int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
     net_out = (float *)p;
   }
   const bool cubic = in_dims[0] == in_dims[1] && in_dims[1] == in_dims[2];
-  // (a program that holds a Conv3DTranspose or a strided Conv3D(2) and nothing but voxel GEMMs runs
-  // on any extents)
-  const bool any_dims = (has_deconv(prog) || has_down(prog)) && fpl_mfma_f32_any_dims(prog);
+  // (a program that holds a Conv3DTranspose, a strided Conv3D(2) or a dilated Conv3D and nothing else
+  // but voxel GEMMs runs on any extents)
+  const bool any_dims = (has_deconv(prog) || has_down(prog) || has_dilated(prog)) && fpl_mfma_f32_any_dims(prog);
   if ((cubic || any_dims) && fpl_mfma_f32_supported(prog) && !getenv("FPL_FORCE_PEROP")) {
     set_last_path(ctx, "mfma_f32");
     FPL_TRY(fpl_forward_mfma_f32_dims(ctx, prog, in_dev, n, in_dims, net_out));
@@ -275,6 +283,9 @@ static int infer_volume_impl(fpl_ctx *ctx, fpl_program *prog, const void *src,
   FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_down(prog),
               "fpl_infer_volume: no 16-bit MFMA kernels for the layer Conv3D(filters, 2, strides=2): this network "
               "runs in fp32 only; use precision f32 (or 'auto')");
+  FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_dilated(prog),
+              "fpl_infer_volume: no 16-bit MFMA kernels for the layer Conv3D(filters, 3, dilation_rate=2): this "
+              "network runs in fp32 only; use precision f32 (or 'auto')");
   // (a Conv3DTranspose has 16-bit / split-half kernels on the graph executor only: gx_exec.h)
   FPL_REQUIRE(ctx, precision == FPL_PREC_F32 || !has_deconv(prog) || (cubic && h16_executor_takes(prog, precision)),
               "fpl_infer_volume: the 16-bit / split-half graph executor does not take this program's "

@@ -996,6 +996,80 @@ __global__ __launch_bounds__(256) void down2_wgrad_partial_f32(
   }
 }
 
+// ---- Conv3D(cout, 3, dilation_rate 2) backward (FPL_L_DILATED; the forward is
+// atrous3_direct_f32, conv_direct.h).  x (n, D, H, W, cin), w [27][cin][cout], dy (n, D-4, H-4,
+// W-4, cout).  No float atomics: the input gradient is gathered, one thread per input element,
+// and the weight gradient is summed in two ordered stages, so equal inputs give equal bits (and
+// fpl_trainer_step runs the whole network in its `fixed_order` mode, as with a Conv3DTranspose).
+// input gradient: dx[m][ci] (+)= sum_t sum_co dy[m - 2t][co] * w[t][ci][co] over the taps whose
+// m - 2t lies inside dy - the 'full' dilated correlation with the flipped kernel
+template <bool ACC>
+__global__ __launch_bounds__(256) void atrous3_dgrad_f32(
+    const float *__restrict__ dy, const float *__restrict__ w, float *__restrict__ dx,
+    int64_t n_in, int D, int H, int W, int cin, int cout) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_in) return;
+  const int od = D - 4, oh = H - 4, ow = W - 4;
+  int64_t t = i;
+  const int ci = (int)(t % cin); t /= cin;
+  const int x = (int)(t % W); t /= W;
+  const int y = (int)(t % H); t /= H;
+  const int z = (int)(t % D); t /= D;
+  float acc = 0.f;
+  for (int tap = 0; tap < 27; ++tap) {
+    const int oz = z - 2 * (tap / 9), oy = y - 2 * ((tap / 3) % 3), ox = x - 2 * (tap % 3);
+    if (oz < 0 || oz >= od || oy < 0 || oy >= oh || ox < 0 || ox >= ow) continue;
+    const float *gp = dy + (((t * od + oz) * oh + oy) * (int64_t)ow + ox) * cout;
+    const float *wp = w + ((int64_t)tap * cin + ci) * cout;
+    for (int co = 0; co < cout; ++co) acc = fmaf(gp[co], wp[co], acc);
+  }
+  dx[i] = ACC ? dx[i] + acc : acc;
+}
+
+// weight gradient, stage 1 (stage 2 is deconv2_wgrad_sum_f32): workgroup (chunk of output voxels,
+// tap): part[chunk][tap][ci][co] = sum_m x[m + 2 tap][ci] * dy[m][co], DC_VS voxels at a time
+// through LDS, each thread its own (ci, co) pair in voxel order
+__global__ __launch_bounds__(256) void atrous3_wgrad_partial_f32(
+    const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ part,
+    int64_t M, int64_t chunk, int D, int H, int W, int cin, int cout) {
+  extern __shared__ float dc_sh[];                 // xs[DC_VS][cin], gs[DC_VS][cout]
+  float *xs = dc_sh, *gs = dc_sh + DC_VS * cin;
+  const int od = D - 4, oh = H - 4, ow = W - 4;
+  const int tap = blockIdx.y;
+  const int dz = 2 * (tap / 9), dyy = 2 * ((tap / 3) % 3), dxx = 2 * (tap % 3);
+  const int64_t m0 = (int64_t)blockIdx.x * chunk;
+  const int64_t m1 = m0 + chunk < M ? m0 + chunk : M;
+  const int npair = cin * cout;
+  float *out = part + ((int64_t)blockIdx.x * 27 + tap) * npair;
+  for (int p0 = 0; p0 < npair; p0 += 256) {        // one (ci, co) pair per thread and pass
+    const int pr = p0 + threadIdx.x;
+    const int ci = pr < npair ? pr / cout : 0, co = pr < npair ? pr % cout : 0;
+    float acc = 0.f;
+    for (int64_t mb = m0; mb < m1; mb += DC_VS) {
+      __syncthreads();
+      for (int e = threadIdx.x; e < DC_VS * cin; e += 256) {
+        const int64_t m = mb + e / cin;
+        float v = 0.f;
+        if (m < m1) {
+          int64_t t = m;
+          const int ox = (int)(t % ow); t /= ow;
+          const int oy = (int)(t % oh); t /= oh;
+          const int oz = (int)(t % od); t /= od;
+          v = x[((((t * D + oz + dz) * H + oy + dyy) * (int64_t)W + ox + dxx) * cin) + e % cin];
+        }
+        xs[e] = v;
+      }
+      for (int e = threadIdx.x; e < DC_VS * cout; e += 256) {
+        const int64_t m = mb + e / cout;
+        gs[e] = m < m1 ? dy[m * cout + e % cout] : 0.f;
+      }
+      __syncthreads();
+      for (int v = 0; v < DC_VS; ++v) acc = fmaf(xs[v * cin + ci], gs[v * cout + co], acc);
+    }
+    if (pr < npair) out[pr] = acc;
+  }
+}
+
 __global__ void adam_update(float *__restrict__ w, const float *__restrict__ g,
                             float *__restrict__ m, float *__restrict__ v,
                             const uint8_t *__restrict__ kind, int64_t n,
@@ -1059,6 +1133,10 @@ int shapes_for(fpl_ctx *ctx, const fpl_trainer *t, const int32_t patch[3],
       case FPL_L_DOWN:
         FPL_REQUIRE(ctx, a.c == L.cin, "layer %zu: strided Conv3D cin mismatch", i);
         o.d = a.d / 2; o.h = a.h / 2; o.w = a.w / 2; o.c = L.cout;
+        break;
+      case FPL_L_DILATED:
+        FPL_REQUIRE(ctx, a.c == L.cin, "layer %zu: dilated Conv3D cin mismatch", i);
+        o.d = a.d - 4; o.h = a.h - 4; o.w = a.w - 4; o.c = L.cout;
         break;
       case FPL_L_POOL:
         FPL_REQUIRE(ctx, L.p[0] == 2 && L.p[1] == 2 && L.p[2] == 2,
@@ -1161,6 +1239,24 @@ int fpl_trainer_create(fpl_ctx *ctx, const fpl_layer *layers, int32_t n_layers,
         for (int j = 0; j < n_layers; ++j)
           FPL_REQUIRE(ctx, !(layers[j].kind == FPL_L_BN && layers[j].src0 == L.dst),
                       "layer %d: a strided Conv3D with a relu activation feeding BatchNorm "
+                      "(layer %d) is not trainable", i, j);
+    } else if (L.kind == FPL_L_DILATED) {
+      FPL_REQUIRE(ctx, L.k == 3 && L.p[0] == 2 && L.p[1] == 2 && L.p[2] == 2,
+                  "layer %d: dilated Conv3D kernel %d dilation (%d,%d,%d) (only kernel 3 with dilation_rate 2)",
+                  i, L.k, L.p[0], L.p[1], L.p[2]);
+      FPL_REQUIRE(ctx, L.cin > 0 && L.cout > 0 && L.cin <= 256 && L.cout <= 256,
+                  "layer %d: dilated Conv3D %d -> %d channels (1 .. 256)", i, L.cin, L.cout);
+      const int64_t kk = (int64_t)27 * L.cin * L.cout;
+      FPL_REQUIRE(ctx, L.w_off[0] >= 0 && L.w_off[0] + kk <= n_weights &&
+                           (!L.use_bias || (L.w_off[1] >= 0 && L.w_off[1] + L.cout <= n_weights)),
+                  "layer %d: weight offsets exceed the arena", i);
+      FPL_REQUIRE(ctx, L.act == FPL_ACT_NONE || L.act == FPL_ACT_RELU,
+                  "layer %d: dilated Conv3D activation %d (none or relu)", i, L.act);
+      FPL_REQUIRE(ctx, L.dst != out_tensor, "layer %d: the head must be a sigmoid conv", i);
+      if (L.act == FPL_ACT_RELU)
+        for (int j = 0; j < n_layers; ++j)
+          FPL_REQUIRE(ctx, !(layers[j].kind == FPL_L_BN && layers[j].src0 == L.dst),
+                      "layer %d: a dilated Conv3D with a relu activation feeding BatchNorm "
                       "(layer %d) is not trainable", i, j);
     } else if (L.kind == FPL_L_BN) {
       FPL_REQUIRE(ctx, L.cin <= 256, "layer %d: > 256 channels", i);
@@ -1325,9 +1421,11 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
   // summed in a fixed order: its convolutions' weight gradients come from conv_wgrad_partial_f32
   // (the fp32 MFMA weight-gradient kernels and conv_wgrad_f32 add their sums with float atomics),
   // and the passes that leave a gradient tensor to those kernels' loaders are not fused.  The
-  // networks without the layer run exactly what they ran before.
+  // networks without the layer run exactly what they ran before.  A network that holds a dilated
+  // Conv3D is new ground in the same way and trains in the same mode: two steps from equal state
+  // give equal bits.
   bool fixed_order = false;
-  for (const fpl_layer &L : t->layers) fixed_order |= L.kind == FPL_L_DECONV;
+  for (const fpl_layer &L : t->layers) fixed_order |= L.kind == FPL_L_DECONV || L.kind == FPL_L_DILATED;
   std::vector<TShape> shp;
   FPL_TRY(shapes_for(ctx, t, patch, &shp));
   const int nt = t->n_tensors;
@@ -1521,6 +1619,13 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
             val[L.dst], n, a.d, a.h, a.w, a.c, o.c, L.act);
         break;
       }
+      case FPL_L_DILATED: {
+        const float *bias = L.use_bias ? t->w + L.w_off[1] : t->zeros;
+        TimedLaunch tl(ctx, "train_atrous_fwd");
+        atrous3_direct_f32<<<g1(n), 256, 0, st>>>(val[L.src0], t->w + L.w_off[0], t->ones, bias,
+            val[L.dst], n, a.d, a.h, a.w, a.c, o.c, L.act);
+        break;
+      }
       case FPL_L_BN: {
         const int C = a.c;
         const int64_t M = (int64_t)batch * a.vox();
@@ -1655,7 +1760,7 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
     if (L.kind == FPL_L_POOL && pool_tiles(shp[ti])) assign[ti] = 1;
     if (L.kind == FPL_L_CONV && use_mfma_bwd && fpl_tm_bwd_supported(L.k, L.cin, L.cout))
       assign[ti] = 1;
-    if (L.kind == FPL_L_DECONV || L.kind == FPL_L_DOWN) assign[ti] = 1;
+    if (L.kind == FPL_L_DECONV || L.kind == FPL_L_DOWN || L.kind == FPL_L_DILATED) assign[ti] = 1;
   }
   for (int ti = 1; ti < nt; ++ti) {
     if (!val[ti]) continue;
@@ -1918,6 +2023,56 @@ int fpl_trainer_step(fpl_trainer *t, const float *data, int data_mem,
           else
             down2_dgrad_f32<true><<<g1(n_in), 256, 0, st>>>(dy, t->w + L.w_off[0], dx, n_in, a.d, a.h,
                                                             a.w, L.cin, L.cout);
+        }
+        break;
+      }
+      case FPL_L_DILATED: {
+        const int64_t M = (int64_t)batch * o.vox();            // output voxels: dy's rows
+        if (L.act == FPL_ACT_RELU) {
+          // as for a conv: the gradient of the pre-activation in place, dy *= (y > 0), before
+          // anything below reads dy
+          const int64_t n4 = n / 4;
+          TimedLaunch tl(ctx, "train_elementwise");
+          if (n4 > 0) {
+            const unsigned gr = (unsigned)std::min<int64_t>(ceil_div64(n4, 256), (int64_t)ctx->n_cu * 8);
+            relu_mask_grad<<<gr, 256, 0, st>>>((const float4 *)val[L.dst], (float4 *)dy, n4);
+          }
+          if (n % 4) relu_mask_grad_tail<<<1, 64, 0, st>>>(val[L.dst], dy, 4 * n4, n);
+        }
+        {
+          // per-workgroup partials summed in chunk order; chunks of >= 256 voxels, as many as
+          // a 64 MB partial buffer allows, at most 256
+          const int64_t per = (int64_t)27 * L.cin * L.cout;
+          const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)64 << 20) / (per * 4)));
+          const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div64(M, 256)));
+          const int64_t chunk = ceil_div64(ceil_div64(M, nchunk), DC_VS) * DC_VS;
+          const int64_t nch = ceil_div64(M, chunk);
+          float *pw;
+          FPL_TRY(alloc_f(nch * per, &pw));
+          TimedLaunch tl(ctx, "train_atrous_wgrad");
+          atrous3_wgrad_partial_f32<<<dim3((unsigned)nch, 27), 256,
+                                      (size_t)DC_VS * (L.cin + L.cout) * sizeof(float), st>>>(
+              val[L.src0], dy, pw, M, chunk, a.d, a.h, a.w, L.cin, L.cout);
+          deconv2_wgrad_sum_f32<<<g1(per), 256, 0, st>>>(pw, (int)nch, per, t->g + L.w_off[0]);
+          tmp.release(pw);
+        }
+        if (L.use_bias) {
+          const int rr = red_rows(M), nb = (int)ceil_div64(M, rr);
+          const int R = std::max(1, 256 / L.cout);
+          TimedLaunch tl(ctx, "train_bias_grad");
+          chan_reduce_partial<2><<<nb, dim3(L.cout, R), (size_t)L.cout * R * 2 * sizeof(double), st>>>(
+              dy, nullptr, nullptr, nullptr, M, L.cout, rr, part);
+          finish_sums<<<L.cout, 256, 0, st>>>(part, nb, L.cout, t->g + L.w_off[1], nullptr, 1.f);
+        }
+        if (dx) {
+          const int64_t n_in = (int64_t)batch * a.elems();
+          TimedLaunch tl(ctx, "train_atrous_dgrad");
+          if (assign[L.src0])
+            atrous3_dgrad_f32<false><<<g1(n_in), 256, 0, st>>>(dy, t->w + L.w_off[0], dx, n_in, a.d, a.h,
+                                                               a.w, L.cin, L.cout);
+          else
+            atrous3_dgrad_f32<true><<<g1(n_in), 256, 0, st>>>(dy, t->w + L.w_off[0], dx, n_in, a.d, a.h,
+                                                              a.w, L.cin, L.cout);
         }
         break;
       }

@@ -23,6 +23,10 @@ numbered as `conv3d_N` with the other convolutions and, read back under such a n
 turn among them.  User-named layers with an edge-2 kernel cannot be told apart by name: they are
 dealt, in file order, to the graph's edge-2 nodes (deconv and down) in creation order, and the
 shape check catches a file that does not fit.
+A Conv3D(filters, 3, dilation_rate=2) (`LayerGraph.dilated`) is a Conv3D to Keras as well: written
+with `dilation_rate [2,2,2]`, numbered as `conv3d_N` with the other convolutions and read back in
+its turn among them - also from a file of user-named layers, whose `(3,3,3,.,.)` kernels are dealt
+to the graph's conv and dilated nodes together, in creation order, under the same shape check.
 
 Files are read with h5py when it is installed and with the package's own reader
 (`h5min`: the HDF5 subset Keras files use) otherwise; they are written with `h5min`.
@@ -124,9 +128,10 @@ def graph_weights_from_layers(graph, layers):
     out = [None] * len(graph.weights)
     ci = bi = di = ei = 0
     for node in graph.nodes:
-        if node.kind not in ('conv', 'bn', 'deconv', 'down'):
+        if node.kind not in ('conv', 'bn', 'deconv', 'down', 'dilated'):
             continue
-        took = node.kind
+        # (a dilated Conv3D is one Keras class with the convolutions: its turn among them)
+        took = 'conv' if node.kind == 'dilated' else node.kind
         if node.kind == 'deconv' and di >= len(deconvs) and ei < len(named2):
             took = 'named2'
         elif node.kind == 'down':
@@ -170,7 +175,7 @@ def _trainable_slots(graph):
     (, bias) / gamma, beta - the moving statistics are not trainable"""
     out = []
     for node in graph.nodes:
-        if node.kind in ('conv', 'deconv', 'down'):
+        if node.kind in ('conv', 'deconv', 'down', 'dilated'):
             out.extend(node.weight_slots)
         elif node.kind == 'bn':
             out.extend(node.weight_slots[:2])
@@ -246,6 +251,7 @@ def weight_tree(graph):
     names in creation order, one group per layer of the graph (weightless ones included,
     as Keras lists them)"""
     roles = {'conv': ['kernel', 'bias'], 'deconv': ['kernel', 'bias'], 'down': ['kernel', 'bias'],
+             'dilated': ['kernel', 'bias'],
              'bn': ['gamma', 'beta', 'moving_mean', 'moving_variance']}
     names = _layer_names(graph)
     layer_names, groups = [], {}
@@ -272,7 +278,7 @@ _KERAS_CLASS = {'conv': ('Conv3D', 'conv3d'), 'bn': ('BatchNormalization', 'batc
                 'crop': ('Cropping3D', 'cropping3d'), 'concat': ('Concatenate', 'concatenate'),
                 'add': ('Add', 'add'), 'input': ('InputLayer', 'input'),
                 'deconv': ('Conv3DTranspose', 'conv3d_transpose'),
-                'down': ('Conv3D', 'conv3d')}
+                'down': ('Conv3D', 'conv3d'), 'dilated': ('Conv3D', 'conv3d')}
 
 
 def _layer_names(graph):
@@ -305,11 +311,12 @@ def model_config(graph):
             spatial = list(graph.in_sz) if graph.in_sz is not None else [None, None, None]
             cfg = {'batch_input_shape': [None] + spatial + [1], 'dtype': 'float32',
                    'sparse': False, 'name': name}
-        elif node.kind in ('conv', 'down'):
+        elif node.kind in ('conv', 'down', 'dilated'):
             k = int(a['k'])
             st = 2 if node.kind == 'down' else 1
+            dl = int(a['d']) if node.kind == 'dilated' else 1
             cfg.update(filters=int(node.channels), kernel_size=[k, k, k], strides=[st, st, st],
-                       padding='valid', data_format='channels_last', dilation_rate=[1, 1, 1],
+                       padding='valid', data_format='channels_last', dilation_rate=[dl, dl, dl],
                        activation=a['activation'] or 'linear', use_bias=bool(a['use_bias']),
                        kernel_initializer=glorot, bias_initializer=zeros,
                        kernel_regularizer=None, bias_regularizer=None,

@@ -9,6 +9,8 @@ graphs use:
            y[2i+a, 2j+b, 2k+c, co] = act(bias[co] + sum_ci x[i,j,k,ci] * W[a,b,c,co,ci])
     down   Conv3D(filters, 2, strides=2), 'valid': the learned 2x down-convolution,
            y[i, j, k, co] = act(bias[co] + sum_{a,b,c,ci} x[2i+a,2j+b,2k+c,ci] * W[a,b,c,ci,co])
+    dilated Conv3D(filters, 3, dilation_rate=2), 'valid', stride 1: the atrous convolution,
+           y[i, j, k, co] = act(bias[co] + sum_{a,b,c,ci} x[i+2a,j+2b,k+2c,ci] * W[a,b,c,ci,co])
     bn     BatchNormalization(axis=-1, momentum=0.99, eps=1e-3)
     relu   Activation('relu')
     pool   MaxPooling3D(2)   (stride 2, floor)
@@ -20,10 +22,10 @@ graphs use:
 Weights are kept as a flat list in Keras `get_weights()` order (layer creation
 order; conv kernel `(kd,kh,kw,Cin,Cout)` then bias; deconv kernel `(2,2,2,Cout,Cin)` -
 Keras' Conv3DTranspose layout, out-channels first - then bias; down kernel `(2,2,2,Cin,Cout)`
-then bias; BN `gamma, beta, moving_mean,
+then bias; dilated kernel `(3,3,3,Cin,Cout)` then bias; BN `gamma, beta, moving_mean,
 moving_var`), so weight lists are interchangeable with the reference's.
 
-`LayerGraph.lower_inference()` folds BN/ReLU/Dropout into the producing conv / deconv / down and
+`LayerGraph.lower_inference()` folds BN/ReLU/Dropout into the producing conv / deconv / down / dilated and
 emits the fused op list + flat fp32 weight arena consumed by `fpl_program_create`
 (include/fplhip.h).
 """
@@ -35,7 +37,7 @@ BN_EPS = 1e-3          # Keras BatchNormalization default epsilon
 BN_MOMENTUM = 0.99     # Keras BatchNormalization default momentum
 
 # fused-op kinds shared with include/fplhip.h (enum fpl_op_kind)
-OP_CONV, OP_POOL, OP_UP, OP_CROP, OP_CONCAT, OP_ADD, OP_DECONV, OP_DOWN = 0, 1, 2, 3, 4, 5, 6, 7
+OP_CONV, OP_POOL, OP_UP, OP_CROP, OP_CONCAT, OP_ADD, OP_DECONV, OP_DOWN, OP_DILATED = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 
 
@@ -147,6 +149,28 @@ class LayerGraph:
         lim = np.sqrt(6.0 / (8 * x.channels + 8 * filters))   # glorot_uniform
         self._new_weight(n, 'kernel', self._rng.uniform(
             -lim, lim, size=(2, 2, 2, x.channels, filters)))
+        if use_bias:
+            self._new_weight(n, 'bias', np.zeros(filters))
+        return n
+
+    def dilated(self, x, filters, use_bias=False, activation=None, kernel_size=3, dilation_rate=2):
+        """Conv3D(filters, 3, dilation_rate=2, padding='valid'): an atrous convolution, 27 taps two
+        voxels apart, stride 1; every axis loses 4.  Kernel `(3,3,3,cin,filters)`, Keras' Conv3D
+        layout, glorot_uniform with fans 27 * cin and 27 * filters (as `conv` with k = 3)."""
+        if tuple(fplutils.to3d(kernel_size)) != (3, 3, 3) or tuple(fplutils.to3d(dilation_rate)) != (2, 2, 2):
+            raise ValueError('dilated: only kernel_size 3 with dilation_rate 2 is supported, got '
+                             'kernel_size %r dilation_rate %r' % (kernel_size, dilation_rate))
+        if activation not in (None, 'relu'):
+            raise ValueError('dilated: activation %r (None or \'relu\')' % (activation,))
+        size = None if x.size is None else tuple(s - 4 for s in x.size)
+        if size is not None and min(size) < 1:
+            raise ValueError('dilated: input %s too small for kernel 3 with dilation_rate 2 '
+                             '(5 voxels per axis)' % (x.size,))
+        n = self._add('dilated', [x], dict(k=3, d=2, use_bias=use_bias, activation=activation),
+                      filters, size)
+        lim = np.sqrt(6.0 / (27 * x.channels + 27 * filters))   # glorot_uniform
+        self._new_weight(n, 'kernel', self._rng.uniform(
+            -lim, lim, size=(3, 3, 3, x.channels, filters)))
         if use_bias:
             self._new_weight(n, 'bias', np.zeros(filters))
         return n
@@ -316,10 +340,10 @@ class LayerGraph:
 
         Returns (ops, arena): `ops` is a list of dicts
             kind, src0, src1, dst, k, cin, cout, act, w_off, scale_off, shift_off,
-            p0..p5 (pool/up factor, crop pairs or deconv / down strides)
+            p0..p5 (pool/up factor, crop pairs, deconv / down strides or the dilation)
         over tensor ids (0 = network input), `arena` the flat fp32 weights:
-        conv kernel as [k^3*cin][cout], deconv kernel as [8][cout][cin], down kernel as
-        [8*cin][cout] (Keras memory order all), then per-channel `scale`, `shift` with
+        conv and dilated kernel as [k^3*cin][cout], deconv kernel as [8][cout][cin], down kernel
+        as [8*cin][cout] (Keras memory order all), then per-channel `scale`, `shift` with
         y = act(scale * conv(x) + shift).
         """
         cons = self.consumers()
@@ -346,7 +370,7 @@ class LayerGraph:
         for n in self.nodes:
             if n.idx in absorbed or n.kind == 'input':
                 continue
-            if n.kind in ('conv', 'deconv', 'down'):
+            if n.kind in ('conv', 'deconv', 'down', 'dilated'):
                 k = n.attrs['k']
                 cin = self.nodes[n.inputs[0]].channels
                 cout = n.channels
@@ -378,9 +402,11 @@ class LayerGraph:
                     last = nxt
                 dst = new_tensor()
                 # (a deconv's kernel stays in Keras' [2][2][2][cout][cin] order; p = the strides)
-                # (a down's kernel is a conv's, [8*cin][cout])
-                strided = n.kind in ('deconv', 'down')
-                ops.append(dict(kind={'conv': OP_CONV, 'deconv': OP_DECONV, 'down': OP_DOWN}[n.kind],
+                # (a down's kernel is a conv's, [8*cin][cout]; a dilated's too, [27*cin][cout], p = the
+                # dilation)
+                strided = n.kind in ('deconv', 'down', 'dilated')
+                ops.append(dict(kind={'conv': OP_CONV, 'deconv': OP_DECONV, 'down': OP_DOWN,
+                                      'dilated': OP_DILATED}[n.kind],
                                 src0=tensor_of[n.inputs[0]],
                                 src1=-1, dst=dst, k=k, cin=cin, cout=cout,
                                 act=act, w_off=push(kern),
@@ -439,7 +465,8 @@ class LayerGraph:
 
 
 # layer kinds shared with include/fplhip.h (enum fpl_layer_kind)
-L_CONV, L_BN, L_RELU, L_POOL, L_DROPOUT, L_UP, L_CROP, L_CONCAT, L_ADD, L_DECONV, L_DOWN = range(11)
+(L_CONV, L_BN, L_RELU, L_POOL, L_DROPOUT, L_UP, L_CROP, L_CONCAT, L_ADD, L_DECONV, L_DOWN,
+ L_DILATED) = range(12)
 
 
 def lower_training(graph):
@@ -459,7 +486,7 @@ def lower_training(graph):
     layers, n_t = [], 1
     kinds = {'conv': L_CONV, 'bn': L_BN, 'relu': L_RELU, 'pool': L_POOL,
              'drop': L_DROPOUT, 'up': L_UP, 'crop': L_CROP, 'concat': L_CONCAT,
-             'add': L_ADD, 'deconv': L_DECONV, 'down': L_DOWN}
+             'add': L_ADD, 'deconv': L_DECONV, 'down': L_DOWN, 'dilated': L_DILATED}
     for n in graph.nodes:
         if n.kind == 'input':
             continue
@@ -468,7 +495,7 @@ def lower_training(graph):
                  dst=n_t, k=0, cin=graph.nodes[n.inputs[0]].channels,
                  cout=n.channels, use_bias=0, act=ACT_NONE, rate=0.0, p=(0,) * 6,
                  w_off=[0, 0, 0, 0])
-        if n.kind in ('conv', 'deconv', 'down'):
+        if n.kind in ('conv', 'deconv', 'down', 'dilated'):
             # a fused relu (unet_like_vol) stays one layer: the engine applies it in the conv
             # epilogue and masks the arriving gradient in the backward pass
             d.update(k=n.attrs['k'], use_bias=int(n.attrs['use_bias']),
@@ -477,7 +504,7 @@ def lower_training(graph):
             d['w_off'][0] = offsets[n.weight_slots[0]]
             if n.attrs['use_bias']:
                 d['w_off'][1] = offsets[n.weight_slots[1]]
-            if n.kind in ('deconv', 'down'):
+            if n.kind in ('deconv', 'down', 'dilated'):
                 d['p'] = (2, 2, 2, 0, 0, 0)
         elif n.kind == 'bn':
             d['w_off'] = [offsets[s] for s in n.weight_slots]

@@ -99,7 +99,16 @@ enum fpl_op_kind {
    * last plane, as MaxPooling3D(2) does.  fp32 executors only: the 16-bit / split precisions
    * refuse a program that holds it.
    * New in ABI 11 - a version 10 library does not know the kind, hence the bump */
-  FPL_OP_DOWN = 7
+  FPL_OP_DOWN = 7,
+  /* Conv3D(cout, 3, dilation_rate=2, 'valid'), an atrous convolution at stride 1 (k = 3,
+   * p0..p2 = 2: the dilation, p3..p5 = 0): y[i][j][k][co] = act(shift[co] + scale[co] *
+   * sum_{a,b,c,ci} x[i+2a][j+2b][k+2c][ci] * W[a][b][c][ci][co]); kernel [27*cin][cout] and
+   * w_off / scale_off / shift_off as for FPL_OP_CONV; every axis loses 4.  fp32 executors
+   * only: the 16-bit / split precisions refuse a program that holds it.
+   * Added without a version bump (FPL_ABI_VERSION stays 11): the change only adds enum
+   * values that older callers never send - no entry point, struct field or layout moved, so
+   * a caller built against the previous header runs unchanged on this library */
+  FPL_OP_DILATED = 8
 };
 enum fpl_act { FPL_ACT_NONE = 0, FPL_ACT_RELU = 1, FPL_ACT_SIGMOID = 2 };
 
@@ -107,13 +116,14 @@ typedef struct fpl_op {
   int32_t kind;      /* fpl_op_kind                                          */
   int32_t src0, src1;/* tensor ids (0 = network input); src1 = -1 if unused  */
   int32_t dst;       /* tensor id produced                                   */
-  int32_t k;         /* conv kernel edge (1 or 3); deconv, down: 2           */
+  int32_t k;         /* conv kernel edge (1 or 3); deconv, down: 2; dilated: 3 */
   int32_t cin, cout; /* channels in / out                                    */
   int32_t act;       /* fpl_act                                              */
   int64_t w_off;     /* offsets (floats) into the weight arena:              */
   int64_t scale_off; /*   kernel [k^3*cin][cout] (Keras memory order),       */
   int64_t shift_off; /*   scale[cout], shift[cout]                           */
-  int32_t p[6];      /* pool/up factors, crop pairs, deconv / down strides   */
+  int32_t p[6];      /* pool/up factors, crop pairs, deconv / down strides,
+                      * dilated: the dilation                                */
 } fpl_op;
 
 /* ---- context -------------------------------------------------------------- */
@@ -286,20 +296,27 @@ enum fpl_layer_kind {
    * [8*cin][cout] at w_off[0], bias at w_off[1]; act none or relu, under the rule stated for
    * convolutions below.  Its own gradients are sums in a fixed order (no float atomics); it
    * does not change which kernels the other layers run.  New in ABI 11 */
-  FPL_L_DOWN = 10
+  FPL_L_DOWN = 10,
+  /* Conv3D(cout, 3, dilation_rate=2, 'valid') (FPL_OP_DILATED): k = 3, p0..p2 = 2 (the
+   * dilation), kernel [27*cin][cout] at w_off[0], bias at w_off[1]; act none or relu, under the
+   * rule stated for convolutions below.  Its gradients are sums in a fixed order (no float
+   * atomics), and in a network that holds it so are the convolutions' weight gradients, as with
+   * FPL_L_DECONV: equal inputs give equal bits.  Added without a version bump, as
+   * FPL_OP_DILATED */
+  FPL_L_DILATED = 11
 };
 typedef struct fpl_layer {
   int32_t kind;        /* fpl_layer_kind                                       */
   int32_t src0, src1;  /* tensor ids (0 = network input)                       */
   int32_t dst;
-  int32_t k, cin, cout;/* conv / deconv / down                                 */
-  int32_t use_bias;    /* conv / deconv / down                                 */
+  int32_t k, cin, cout;/* conv / deconv / down / dilated                       */
+  int32_t use_bias;    /* conv / deconv / down / dilated                       */
   int32_t act;         /* conv / deconv activation (fpl_act): relu on any conv but the
                         * head (applied in the conv epilogue, its gradient masked
                         * in place in the backward pass; not in front of a BN),
                         * sigmoid on the head and only there                    */
   float rate;          /* dropout                                              */
-  int32_t p[6];        /* pool/up factors or crop pairs                        */
+  int32_t p[6];        /* pool/up factors, crop pairs, strides or the dilation */
   int64_t w_off[4];    /* offsets (floats) into the weight arena: conv kernel,
                         * bias | BN gamma, beta, moving_mean, moving_variance   */
 } fpl_layer;

@@ -1311,6 +1311,111 @@ def down_bench(ctx, torch, vol=390, reps=5):
     return out
 
 
+def dilated_bench(ctx, torch, vol=390, reps=5):
+    """the example network with two Conv3D(filters, 3, dilation_rate=2) end to end, its training
+    step, and the kernel alone beside the plain conv3_f32 at the same widths and output count
+    (the same flops, and a kernel this project has measured)"""
+    from flypylib_amd import FplNetwork, _capi
+    from flypylib_amd.program import LayerGraph
+    from tests import dilated_cases as di
+
+    def stats(v):
+        return {'median': round(float(np.median(v)), 4), 'min': round(float(min(v)), 4),
+                'max': round(float(max(v)), 4)}
+
+    def table():
+        return {k: {'ms': round(v['ms'], 4), 'launches': int(v['launches'])}
+                for k, v in sorted(ctx.timing_get().items(), key=lambda kv: -kv[1]['ms'])}
+    out = {'reps': reps, 'note': 'one warm-up, then median / min / max of %d; resident source and '
+                                 'destination; no gate: the path did not exist before' % reps}
+    # ---- tiny_atrous over a volume: tile 105, pitch 95, 4 tiles per axis of 390 ----------------
+    tile = 105
+    net = FplNetwork(lambda in_sz=None: di.tiny_atrous_random((tile,) * 3 if in_sz is None else in_sz))
+    net._set_infer()
+    src = torch.from_numpy(np.random.default_rng(0).standard_normal((vol,) * 3).astype(np.float32)).to('cuda:0')
+    dst = torch.empty((vol,) * 3, dtype=torch.float32, device='cuda:0')
+    prog = net.infer_network.program
+    kw = dict(precision=_capi.PREC_F32, dst=dst, dims=(vol,) * 3)
+    ms = []
+    for r in range(reps + 1):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        prog.infer_volume(src, net.infer_sz, net.rf_offset, **kw)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    path = ctx.last_path()
+    ctx.timing(True); ctx.timing_reset()
+    prog.infer_volume(src, net.infer_sz, net.rf_offset, **kw)
+    kern = table()
+    ctx.timing(False)
+    out['tiny_atrous_infer'] = {'volume': [vol] * 3, 'tile_in': tile, 'pitch': tile - 10, 'executor': path,
+                                'ms': stats(ms[1:]), 'runs_ms': [round(x, 3) for x in ms[1:]],
+                                'mvox_s': round(vol ** 3 / np.median(ms[1:]) / 1e3, 1), 'kernels_one_pass': kern}
+    print('infer', json.dumps(out['tiny_atrous_infer']['ms']), flush=True)
+    del src, dst
+    # ---- its training step -------------------------------------------------------------------
+    batch, patch = 8, 62
+    g = di.tiny_atrous((patch,) * 3)[0]
+    rng = np.random.default_rng(1)
+    x = torch.from_numpy(rng.standard_normal((batch,) + (patch,) * 3 + (1,)).astype(np.float32)).to('cuda:0')
+    y = torch.from_numpy((rng.random((batch,) + (patch - 10,) * 3 + (1,)) < 0.3).astype(np.uint8)).to('cuda:0')
+    tr = _capi.Trainer(ctx, g)
+    ms = []
+    for r in range(reps + 1):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        tr.step(x, y, seed=r); tr.apply(1.0)
+        ctx.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    ctx.timing(True); ctx.timing_reset()
+    tr.step(x, y, seed=0); tr.apply(1.0)
+    ctx.synchronize()
+    kern = table()
+    ctx.timing(False)
+    tr.close()
+    out['tiny_atrous_train_step'] = {
+        'batch': batch, 'patch': patch, 'ms': stats(ms[1:]), 'runs_ms': [round(v, 3) for v in ms[1:]],
+        'note': 'direct fp32 kernels for the layer; fixed-order weight gradients for every convolution',
+        'kernels_one_step': kern}
+    print('train', json.dumps(out['tiny_atrous_train_step']['ms']), flush=True)
+    del x, y
+    # ---- the kernel alone, beside the plain 3x3x3 ---------------------------------------------
+    def kernel_ms(graph, xin, yshape, name):
+        p = _capi.Program(ctx, graph)
+        yout = torch.empty(yshape, dtype=torch.float32, device='cuda:0')
+        v = []
+        for r in range(reps + 1):
+            ctx.timing(True); ctx.timing_reset()
+            p.forward_device(xin, out=yout)
+            t = ctx.timing_get()
+            ctx.timing(False)
+            v.append(t[name]['ms'])
+        p.close()
+        return v[1:]
+    alone = {}
+    for cin, cout, n, edge in ((16, 16, 8, 100), (48, 48, 2, 100), (96, 32, 2, 84)):
+        oe = edge - 4
+        xin = torch.randn((n,) + (edge,) * 3, device='cuda:0')
+        g, _ = di.dilated_graph(cin, cout, 1, 1, 1, (edge,) * 3)
+        k_ms = kernel_ms(g, xin, (n,) + (oe,) * 3 + (cout,), 'mfma_atrous3_f32')
+        # the comparator: conv1(1 -> cin) | conv3(cin -> cout) BN ReLU on an input two voxels
+        # smaller, so that both kernels write (edge - 4)^3 voxels
+        pg = LayerGraph((edge - 2,) * 3)
+        pg.finish(pg.conv_bn_relu(pg.conv(pg.input(), cin, 1, use_bias=True), cout, 3))
+        di.randomize(pg, 1)
+        p_ms = kernel_ms(pg, xin[:, :edge - 2, :edge - 2, :edge - 2].contiguous(), (n,) + (oe,) * 3 + (cout,),
+                         'mfma_conv3_f32')
+        del xin
+        km, pm = float(np.median(k_ms)), float(np.median(p_ms))
+        flop = 2.0 * n * oe ** 3 * 27 * cin * cout
+        key = '%dto%d_%dx%d' % (cin, cout, n, edge)
+        alone[key] = {'output_voxels': n * oe ** 3, 'flop': flop, 'kernel_ms': stats(k_ms),
+                      'tflops': round(flop / km / 1e9, 2), 'conv3_f32_same_outputs_ms': stats(p_ms),
+                      'conv3_f32_tflops': round(flop / pm / 1e9, 2), 'kernel_over_conv3_f32': round(km / pm, 3)}
+        print(key, json.dumps(alone[key]), flush=True)
+    out['atrous_kernel_alone'] = alone
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mine-size', type=int, default=520)
@@ -1559,6 +1664,11 @@ def main():
         res['down'] = down_bench(ctx, torch)
         if a.out is None:
             a.out = os.path.join(ROOT, 'profiles', 'down.json')
+
+    if 'dilated' in what:
+        res['dilated'] = dilated_bench(ctx, torch)
+        if a.out is None:
+            a.out = os.path.join(ROOT, 'profiles', 'dilated.json')
 
     if 'train_gen' in what:
         res['train_gen'] = train_gen(ctx, torch)
