@@ -1621,15 +1621,35 @@ bool fpl_mfma_f32_any_dims(const fpl_program *prog) {
   return true;
 }
 
-// every op kind; conv3 needs cout <= 64 and <= 12 channel chunks
+// Exactly the programs fpl_forward_mfma_f32_dims can run; the dispatchers (fpl_program_forward,
+// fpl_infer_volume) send everything else to the per-op executor.  Every op kind, within:
+//  * up / crop views and virtual concatenations are read by multi-channel 3x3x3 convs only (an add
+//    may read crops); a concatenation that such a conv reads starts its second operand on a
+//    16-channel chunk: the first operand's channel count is a multiple of 16
+//  * 3x3x3, cin > 1: <= 12 channel chunks of 16, <= 256 outputs (slices of 64 per launch)
+//  * 3x3x3, cin = 1 (stem_cin1_f32<1..4>): <= 64 outputs
+//  * 1x1x1 (conv1_f32<1, 2, 3, 4, 6, 8>): <= 64, 81..96 or 113..128 outputs
+//  * pools of 2, ups of 1 or 2, crops equal on all six faces, 2x2x2 deconv / down <= 256 channels
 bool fpl_mfma_f32_supported(const fpl_program *prog) {
   // tensors that exist only as an index remap (up / crop / concat): consumable by a
   // multi-channel conv3 (its tile loader applies the remap), nothing else
   std::vector<char> is_view(prog->n_tensors, 0);       // 1: up / crop view, 2: virtual concatenation
   const std::vector<char> written = concats_written(prog);
+  // channels per tensor, and of the first operand of the concatenation that made it (else 0)
+  std::vector<int> ch(prog->n_tensors, 0), cat_first(prog->n_tensors, 0);
+  ch[0] = 1;
   for (size_t i = 0; i < prog->ops.size(); ++i) {
     const fpl_op &op = prog->ops[i];
     const bool v0 = is_view[op.src0], v1 = op.src1 >= 0 && is_view[op.src1];
+    const bool makes_channels = op.kind == FPL_OP_CONV || op.kind == FPL_OP_DECONV ||
+                                op.kind == FPL_OP_DOWN || op.kind == FPL_OP_DILATED;
+    ch[op.dst] = makes_channels ? op.cout : ch[op.src0];
+    if (op.kind == FPL_OP_CONCAT) {
+      ch[op.dst] = ch[op.src0] + ch[op.src1];
+      cat_first[op.dst] = ch[op.src0];
+    }
+    // (the conv3 resolves a concatenation through its two operands, written out or not)
+    if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1 && cat_first[op.src0] % 16 != 0) return false;
     if (op.kind == FPL_OP_UP || op.kind == FPL_OP_CROP) {
       if (v0) return false;
       is_view[op.dst] = 1;
@@ -1658,7 +1678,9 @@ bool fpl_mfma_f32_supported(const fpl_program *prog) {
       return false;
     if (op.kind == FPL_OP_CONV) {
       if (op.k == 3 && (op.cout > 256 || op.cin > 12 * 16)) return false;
-      if (op.k == 1 && op.cout > 128) return false;
+      if (op.k == 3 && op.cin == 1 && op.cout > 64) return false;       // stem_cin1_f32<1..4>
+      const int mb = (op.cout + 15) / 16;
+      if (op.k == 1 && (mb > 8 || mb == 5 || mb == 7)) return false;    // conv1_f32<1, 2, 3, 4, 6, 8>
     }
     if (op.kind == FPL_OP_DECONV && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
     if (op.kind == FPL_OP_DOWN && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
