@@ -16,6 +16,7 @@
 
 #include "fast_paths.h"
 #include "mfma_util.h"
+#include "mfma_f32_plan.h"
 
 namespace {
 
@@ -1321,7 +1322,7 @@ __global__ void pool2_f32v(const float *__restrict__ x, float *__restrict__ y, i
 void pack_conv3_f32(const float *W, const float *scale, int cin, int cout, int mb,
                     std::vector<float> *out, int co0 = 0) {
   const int ncc = (cin + 15) / 16;
-  out->assign((size_t)ncc * 27 * mb * 256, 0.f);
+  out->assign(f32plan::conv3_frag_floats(cin, mb), 0.f);
   for (int cc = 0; cc < ncc; ++cc)
     for (int tap = 0; tap < 27; ++tap)
       for (int b = 0; b < mb; ++b)
@@ -1340,7 +1341,7 @@ void pack_conv3_f32(const float *W, const float *scale, int cin, int cout, int m
 void pack_conv1_f32(const float *W, const float *scale, int cin, int cout, int mb,
                     std::vector<float> *out) {
   const int nkb = (cin + 15) / 16;
-  out->assign((size_t)nkb * mb * 256, 0.f);
+  out->assign(f32plan::conv1_frag_floats(cin, mb), 0.f);
   for (int kb = 0; kb < nkb; ++kb)
     for (int b = 0; b < mb; ++b)
       for (int lane = 0; lane < 64; ++lane) {
@@ -1358,8 +1359,8 @@ void pack_conv1_f32(const float *W, const float *scale, int cin, int cout, int m
 // with N = 16 nb + (lane & 15) = c' * cout + co inside the (a, b) row, then the shifts by N
 void pack_deconv_f32(const float *W, const float *scale, const float *shift, int cin, int cout,
                      std::vector<float> *out) {
-  const int nkb = (cin + 15) / 16, nb2 = (2 * cout + 15) / 16;
-  out->assign((size_t)4 * nb2 * nkb * 256 + (size_t)16 * nb2, 0.f);
+  const int nkb = (cin + 15) / 16, nb2 = f32plan::deconv_nb2(cout);
+  out->assign(f32plan::deconv_frag_floats(cin, cout), 0.f);
   for (int ab = 0; ab < 4; ++ab)
     for (int nb = 0; nb < nb2; ++nb)
       for (int kb = 0; kb < nkb; ++kb)
@@ -1374,7 +1375,7 @@ void pack_deconv_f32(const float *W, const float *scale, const float *shift, int
                 W[((size_t)tap * cout + co) * cin + ci] * scale[co];
           }
         }
-  float *sh = out->data() + (size_t)4 * nb2 * nkb * 256;
+  float *sh = out->data() + f32plan::deconv_shift_off(cin, cout);
   for (int n = 0; n < 2 * cout; ++n) sh[n] = shift[n % cout];
 }
 
@@ -1393,24 +1394,14 @@ int launch_deconv(fpl_ctx *ctx, DeconvF &a) {
   return 0;
 }
 
-// the instance of down2_f32 that runs cin -> cout: K-blocks per tap pair held in registers
-// (0: the any-cin form) and the N-blocks per pass, which the fragments are padded to
-static void down_form(int cin, int *nkb_reg, int *nbt) {
-  const int nkb = (2 * cin + 15) / 16;
-  *nkb_reg = nkb <= 2 ? nkb : 0;
-  *nbt = nkb <= 2 ? 2 : 4;
-}
-
 // down fragments [ab][kb][nb][lane][j] = W[ab][kk = 16 kb + 4g + j][co = 16 nb + (lane & 15)] *
 // scale[co] with kk = c * cin + ci inside the (a, b) tap pair (the kernel's own memory order:
 // [a][b][c][ci][co]), then the shifts, both padded with zeros to nbp N-blocks
 void pack_down_f32(const float *W, const float *scale, const float *shift, int cin, int cout,
                    std::vector<float> *out) {
-  int nkb_reg, nbt;
-  down_form(cin, &nkb_reg, &nbt);
   const int k2 = 2 * cin, nkb = (k2 + 15) / 16;
-  const int nbp = ((cout + 15) / 16 + nbt - 1) / nbt * nbt;
-  out->assign((size_t)4 * nkb * nbp * 256 + (size_t)16 * nbp, 0.f);
+  const int nbp = f32plan::down_nbp(cin, cout);
+  out->assign(f32plan::down_frag_floats(cin, cout), 0.f);
   for (int ab = 0; ab < 4; ++ab)
     for (int kb = 0; kb < nkb; ++kb)
       for (int nb = 0; nb < nbp; ++nb)
@@ -1424,13 +1415,13 @@ void pack_down_f32(const float *W, const float *scale, const float *shift, int c
                 W[((size_t)ab * k2 + kk) * cout + co] * scale[co];
           }
         }
-  float *sh = out->data() + (size_t)4 * nkb * nbp * 256;
+  float *sh = out->data() + f32plan::down_shift_off(cin, cout);
   for (int co = 0; co < cout; ++co) sh[co] = shift[co];
 }
 
 int launch_down(fpl_ctx *ctx, DownF &a) {
   int nkb_reg, nbt;
-  down_form(a.cin, &nkb_reg, &nbt);
+  f32plan::down_form(a.cin, &nkb_reg, &nbt);
   // as instantiated below (two voxel groups with two K-blocks per tap pair in registers took 132 VGPRs)
   const int G = nkb_reg == 2 ? 1 : 2;
   const int64_t groups = ceil_div64(a.M, 16 * G);
@@ -1446,7 +1437,7 @@ int launch_down(fpl_ctx *ctx, DownF &a) {
 
 // stem fragments [q][mb][lane][j] = W[tap = 16q + 4g + j][0][16mb + (lane&15)] * scale
 void pack_stem_f32(const float *W, const float *scale, int cout, int mb, std::vector<float> *out) {
-  out->assign((size_t)2 * mb * 256, 0.f);
+  out->assign(f32plan::stem_frag_floats(mb), 0.f);
   for (int q = 0; q < 2; ++q)
     for (int b = 0; b < mb; ++b)
       for (int lane = 0; lane < 64; ++lane) {
@@ -1472,8 +1463,7 @@ int launch_stem(fpl_ctx *ctx, StemF &a, int n) {
 
 struct F32State {
   uint64_t version = ~0ull;
-  float *frags = nullptr;
-  std::vector<size_t> off;       // per op (float offset), conv ops only
+  float *frags = nullptr;          // laid out by the plan (mfma_f32_plan.h: Step::frag_off)
 };
 
 void f32_state_free(fpl_ctx *, void *p) {
@@ -1482,11 +1472,11 @@ void f32_state_free(fpl_ctx *, void *p) {
   delete s;
 }
 
-// virtual tensor view: a real f32 buffer seen through up / crop
-struct View {
+// a plan's view (f32plan::View) at run time: a real f32 buffer seen through up / crop
+struct TensorView {
   const float *p = nullptr;
   int D = 0, C = 0;              // real buffer dims (cubic tiles) and channels
-  int H = 0, W = 0;              // = D but in a program of voxel GEMMs only (fpl_mfma_f32_any_dims)
+  int H = 0, W = 0;              // = D but in a program of voxel GEMMs only (Plan::any_dims)
   int up = 1, crop = 0;
   int dim = 0;                   // logical (viewed) edge
 };
@@ -1589,106 +1579,14 @@ int launch1(fpl_ctx *ctx, Conv1F &a) {
 
 }  // namespace
 
-// A concatenation stays virtual (two views, resolved by the conv3 that loads it) in every
-// program of the kinds the executor has always run.  In a program that holds a
-// Conv3DTranspose - new ground - one whose readers are not all multi-channel conv3s is
-// written out instead, so that a 1x1x1 conv may read it.  One pass per program: per op,
-// 1 = a concatenation that is written out.
-static std::vector<char> concats_written(const fpl_program *prog) {
-  std::vector<char> other_reader(prog->n_tensors, 0), out(prog->ops.size(), 0);
-  bool deconv = false;
-  other_reader[prog->out_tensor] = 1;
-  for (auto &op : prog->ops) {
-    deconv |= op.kind == FPL_OP_DECONV;
-    if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1) continue;
-    other_reader[op.src0] = 1;
-    if (op.src1 >= 0) other_reader[op.src1] = 1;
-  }
-  if (deconv)
-    for (size_t i = 0; i < prog->ops.size(); ++i)
-      out[i] = prog->ops[i].kind == FPL_OP_CONCAT && other_reader[prog->ops[i].dst];
-  return out;
+static f32plan::Plan plan_of(const fpl_program *prog, bool unfused = false) {
+  return f32plan::plan(prog->ops.data(), prog->ops.size(), prog->n_tensors, prog->out_tensor, unfused);
 }
 
-// programs made of voxel GEMMs (1x1x1 convs, Conv3DTransposes and strided Conv3D(2)s) and dilated
-// Conv3Ds, whose kernel takes three extents, run on tiles of any extents; everything else is
-// written for cubic tiles
-bool fpl_mfma_f32_any_dims(const fpl_program *prog) {
-  for (auto &op : prog->ops)
-    if (!(op.kind == FPL_OP_DECONV || op.kind == FPL_OP_DOWN || op.kind == FPL_OP_DILATED ||
-          (op.kind == FPL_OP_CONV && op.k == 1)))
-      return false;
-  return true;
-}
-
-// Exactly the programs fpl_forward_mfma_f32_dims can run; the dispatchers (fpl_program_forward,
-// fpl_infer_volume) send everything else to the per-op executor.  Every op kind, within:
-//  * up / crop views and virtual concatenations are read by multi-channel 3x3x3 convs only (an add
-//    may read crops); a concatenation that such a conv reads starts its second operand on a
-//    16-channel chunk: the first operand's channel count is a multiple of 16
-//  * 3x3x3, cin > 1: <= 12 channel chunks of 16, <= 256 outputs (slices of 64 per launch)
-//  * 3x3x3, cin = 1 (stem_cin1_f32<1..4>): <= 64 outputs
-//  * 1x1x1 (conv1_f32<1, 2, 3, 4, 6, 8>): <= 64, 81..96 or 113..128 outputs
-//  * pools of 2, ups of 1 or 2, crops equal on all six faces, 2x2x2 deconv / down <= 256 channels
-bool fpl_mfma_f32_supported(const fpl_program *prog) {
-  // tensors that exist only as an index remap (up / crop / concat): consumable by a
-  // multi-channel conv3 (its tile loader applies the remap), nothing else
-  std::vector<char> is_view(prog->n_tensors, 0);       // 1: up / crop view, 2: virtual concatenation
-  const std::vector<char> written = concats_written(prog);
-  // channels per tensor, and of the first operand of the concatenation that made it (else 0)
-  std::vector<int> ch(prog->n_tensors, 0), cat_first(prog->n_tensors, 0);
-  ch[0] = 1;
-  for (size_t i = 0; i < prog->ops.size(); ++i) {
-    const fpl_op &op = prog->ops[i];
-    const bool v0 = is_view[op.src0], v1 = op.src1 >= 0 && is_view[op.src1];
-    const bool makes_channels = op.kind == FPL_OP_CONV || op.kind == FPL_OP_DECONV ||
-                                op.kind == FPL_OP_DOWN || op.kind == FPL_OP_DILATED;
-    ch[op.dst] = makes_channels ? op.cout : ch[op.src0];
-    if (op.kind == FPL_OP_CONCAT) {
-      ch[op.dst] = ch[op.src0] + ch[op.src1];
-      cat_first[op.dst] = ch[op.src0];
-    }
-    // (the conv3 resolves a concatenation through its two operands, written out or not)
-    if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1 && cat_first[op.src0] % 16 != 0) return false;
-    if (op.kind == FPL_OP_UP || op.kind == FPL_OP_CROP) {
-      if (v0) return false;
-      is_view[op.dst] = 1;
-    } else if (op.kind == FPL_OP_CONCAT) {
-      if (written[i]) {
-        // operands: buffers or up / crop views of buffers, not a virtual concatenation
-        if (is_view[op.src0] == 2 || is_view[op.src1] == 2) return false;
-      } else {
-        is_view[op.dst] = 2;
-      }
-    } else if (op.kind == FPL_OP_CONV && op.k == 3 && op.cin > 1) {
-      if (v1) return false;
-    } else if (op.kind == FPL_OP_ADD) {
-      // operands may be cropped views (checked for up / concat at run time)
-    } else if (v0 || v1) {
-      return false;
-    }
-    if (prog->out_tensor == op.dst && is_view[op.dst]) return false;
-  }
-  for (auto &op : prog->ops) {
-    if (op.kind == FPL_OP_POOL && (op.p[0] != 2 || op.p[1] != 2 || op.p[2] != 2)) return false;
-    if (op.kind == FPL_OP_UP && (op.p[0] != op.p[1] || op.p[1] != op.p[2] || (op.p[0] != 1 && op.p[0] != 2)))
-      return false;
-    if (op.kind == FPL_OP_CROP && !(op.p[0] == op.p[1] && op.p[1] == op.p[2] && op.p[2] == op.p[3] &&
-                                    op.p[3] == op.p[4] && op.p[4] == op.p[5]))
-      return false;
-    if (op.kind == FPL_OP_CONV) {
-      if (op.k == 3 && (op.cout > 256 || op.cin > 12 * 16)) return false;
-      if (op.k == 3 && op.cin == 1 && op.cout > 64) return false;       // stem_cin1_f32<1..4>
-      const int mb = (op.cout + 15) / 16;
-      if (op.k == 1 && (mb > 8 || mb == 5 || mb == 7)) return false;    // conv1_f32<1, 2, 3, 4, 6, 8>
-    }
-    if (op.kind == FPL_OP_DECONV && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
-    if (op.kind == FPL_OP_DOWN && (op.k != 2 || op.cin > 256 || op.cout > 256)) return false;
-    // (the widths of the plain 3x3x3: 12 channel chunks, slices of 64 outputs)
-    if (op.kind == FPL_OP_DILATED && (op.k != 3 || op.cout > 256 || op.cin > 12 * 16)) return false;
-  }
-  return true;
-}
+// Exactly the programs fpl_forward_mfma_f32_dims can run, as mfma_f32_plan.h states them; the
+// dispatchers (fpl_program_forward, fpl_infer_volume) send everything else to the per-op executor
+bool fpl_mfma_f32_supported(const fpl_program *prog) { return plan_of(prog).ok; }
+bool fpl_mfma_f32_takes(const fpl_program *prog, bool cubic) { return plan_of(prog).takes(cubic); }
 
 // in: (n, T,T,T) f32 on the device (cubic tiles); out: (n, d,d,d, c) f32
 int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T,
@@ -1697,12 +1595,22 @@ int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n
   return fpl_forward_mfma_f32_dims(ctx, prog, in, n, dims, out);
 }
 
-// ... or (n, dims) tiles of any extents for a program of voxel GEMMs (fpl_mfma_f32_any_dims)
+// the plan admits no program that reaches this: its tables (mfma_f32_plan.h) are the cases of the
+// switches below
+static int no_instance(fpl_ctx *ctx, const f32plan::Step &s, int mb) {
+  return fpl_fail(ctx, "op %d: no %s kernel for %d blocks of 16 outputs (mfma_f32_plan.h admits none)", s.op[0],
+                  f32plan::form_name(s.form), mb);
+}
+
+// ... or (n, dims) tiles of any extents for a program of voxel GEMMs (Plan::any_dims)
 int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, int n,
                               const int32_t dims[3], float *out) {
-  FPL_REQUIRE(ctx, fpl_mfma_f32_supported(prog), "program has ops the fp32 MFMA executor lacks");
+  using namespace f32plan;
+  // FPL_F32_UNFUSED=1: one kernel per op, for A/B runs.  Read per forward: it may change between two
+  const Plan plan = plan_of(prog, getenv("FPL_F32_UNFUSED") != nullptr);
+  FPL_REQUIRE(ctx, plan.ok, "program has ops the fp32 MFMA executor lacks (op %d: %s)", plan.bad_op, plan.reason);
   const int T = dims[0];
-  FPL_REQUIRE(ctx, (dims[0] == dims[1] && dims[1] == dims[2]) || fpl_mfma_f32_any_dims(prog),
+  FPL_REQUIRE(ctx, (dims[0] == dims[1] && dims[1] == dims[2]) || plan.any_dims,
               "the fp32 MFMA executor runs this program on cubic tiles only");
   F32State *st = (F32State *)prog->fast_state_f32;
   if (!st) {
@@ -1712,53 +1620,43 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
   }
   const float *A = prog->arena_host.data();
   if (st->version != prog->arena_version) {
-    std::vector<float> all;
-    st->off.assign(prog->ops.size(), 0);
-    for (size_t i = 0; i < prog->ops.size(); ++i) {
-      const fpl_op &op = prog->ops[i];
-      if (op.kind == FPL_OP_DECONV) {
-        std::vector<float> f;
-        pack_deconv_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
-        st->off[i] = all.size();
-        all.insert(all.end(), f.begin(), f.end());
-        continue;
+    std::vector<float> all(plan.frag_floats), f;
+    auto put = [&](size_t off) {
+      if (off + f.size() > all.size()) return fpl_fail(ctx, "fp32 MFMA fragments: a block leaves the plan's buffer");
+      std::copy(f.begin(), f.end(), all.begin() + off);
+      return 0;
+    };
+    for (const Step &s : plan.steps) {
+      const fpl_op &op = prog->ops[s.op[0]];
+      const float *W = A + op.w_off, *scale = A + op.scale_off;
+      switch (s.form) {
+        case DECONV:
+          pack_deconv_f32(W, scale, A + op.shift_off, op.cin, op.cout, &f);
+          FPL_TRY(put(s.frag_off));
+          break;
+        case DOWN:
+          pack_down_f32(W, scale, A + op.shift_off, op.cin, op.cout, &f);
+          FPL_TRY(put(s.frag_off));
+          break;
+        case STEM: case STEM_CONV1_POOL:
+          pack_stem_f32(W, scale, op.cout, s.mb, &f);
+          FPL_TRY(put(s.frag_off));
+          break;
+        case CONV1:
+          pack_conv1_f32(W, scale, op.cin, op.cout, s.mb, &f);
+          FPL_TRY(put(s.frag_off));
+          break;
+        default:                                  // the 3x3x3 forms: their slices; pool, add, concat: none
+          for (int q = 0; q < s.n_slices; ++q) {
+            pack_conv3_f32(W, scale, op.cin, op.cout, s.slice[q].mb, &f, s.slice[q].c0);
+            FPL_TRY(put(s.slice[q].frag_off));
+          }
       }
-      if (op.kind == FPL_OP_DOWN) {
-        std::vector<float> f;
-        pack_down_f32(A + op.w_off, A + op.scale_off, A + op.shift_off, op.cin, op.cout, &f);
-        st->off[i] = all.size();
-        all.insert(all.end(), f.begin(), f.end());
-        continue;
+      if (s.mb1) {
+        const fpl_op &n1 = prog->ops[s.op[1]];
+        pack_conv1_f32(A + n1.w_off, A + n1.scale_off, n1.cin, n1.cout, s.mb1, &f);
+        FPL_TRY(put(s.frag1_off));
       }
-      if (op.kind == FPL_OP_DILATED) {
-        // the plain 3x3x3's fragments: 64 output channels per launch, slices back to back
-        std::vector<float> f;
-        for (int c0 = 0; c0 < op.cout; c0 += 64) {
-          std::vector<float> fs;
-          pack_conv3_f32(A + op.w_off, A + op.scale_off, op.cin, op.cout,
-                         (std::min(64, op.cout - c0) + 15) / 16, &fs, c0);
-          f.insert(f.end(), fs.begin(), fs.end());
-        }
-        st->off[i] = all.size();
-        all.insert(all.end(), f.begin(), f.end());
-        continue;
-      }
-      if (op.kind != FPL_OP_CONV) continue;
-      std::vector<float> f;
-      const int mb = (op.cout + 15) / 16;
-      if (op.k == 3 && op.cin == 1) pack_stem_f32(A + op.w_off, A + op.scale_off, op.cout, mb, &f);
-      else if (op.k == 3) {
-        // 64 output channels per launch: slices back to back
-        for (int c0 = 0; c0 < op.cout; c0 += 64) {
-          std::vector<float> fs;
-          pack_conv3_f32(A + op.w_off, A + op.scale_off, op.cin, op.cout,
-                         (std::min(64, op.cout - c0) + 15) / 16, &fs, c0);
-          f.insert(f.end(), fs.begin(), fs.end());
-        }
-      }
-      else pack_conv1_f32(A + op.w_off, A + op.scale_off, op.cin, op.cout, mb, &f);
-      st->off[i] = all.size();
-      all.insert(all.end(), f.begin(), f.end());
     }
     if (st->frags) FPL_HIP(ctx, hipFree(st->frags));
     st->frags = nullptr;
@@ -1767,268 +1665,195 @@ int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, 
     st->version = prog->arena_version;
   }
   DevTemp tmp(ctx);
-  const std::vector<char> written = concats_written(prog);
-  std::vector<View> view(prog->n_tensors);
-  view[0].p = in; view[0].D = T; view[0].H = dims[1]; view[0].W = dims[2]; view[0].C = 1; view[0].dim = T;
+  std::vector<TensorView> buf(prog->n_tensors);         // the materialised tensors
+  buf[0].p = in; buf[0].D = T; buf[0].H = dims[1]; buf[0].W = dims[2]; buf[0].C = 1; buf[0].dim = T;
+  auto seen = [&](const f32plan::View &v) {
+    TensorView r = buf[v.tensor];
+    r.up = v.up; r.crop = v.crop; r.dim = r.D * v.up - 2 * v.crop;
+    return r;
+  };
   hipStream_t stm = ctx->stream;
-  auto cube = [](int d) { return (int64_t)d * d * d; };
-  for (size_t i = 0; i < prog->ops.size(); ++i) {
+  for (const Step &s : plan.steps) {
+    const int i = s.op[0];
     const fpl_op &op = prog->ops[i];
-    const View a = view[op.src0];
-    FPL_REQUIRE(ctx, a.dim > 0, "op %zu reads a tensor before it is produced", i);
-    View o;
-    switch (op.kind) {
-      case FPL_OP_UP:
-        FPL_REQUIRE(ctx, a.up == 1 && a.crop == 0, "op %zu: nested views", i);
-        o = a; o.up = op.p[0]; o.dim = a.dim * op.p[0];
-        view[op.dst] = o;
-        continue;
-      case FPL_OP_CROP:
-        FPL_REQUIRE(ctx, a.up == 1 && a.crop == 0, "op %zu: nested views", i);
-        o = a; o.crop = op.p[0]; o.dim = a.dim - 2 * op.p[0];
-        view[op.dst] = o;
-        continue;
-      case FPL_OP_CONCAT: {
-        // kept virtual: remembered as two views; only a conv3 may consume it
-        const View b = view[op.src1];
-        FPL_REQUIRE(ctx, a.dim == b.dim, "op %zu: concatenate of %d^3 with %d^3 - input size is "
-                    "not compatible with this architecture", i, a.dim, b.dim);
-        if (written[i]) {
-          FPL_REQUIRE(ctx, a.p && b.p, "op %zu: concatenate of a concatenation", i);
-          const int64_t no = (int64_t)n * cube(a.dim) * (a.C + b.C);
-          float *cdst = out;
-          if (op.dst != prog->out_tensor) {
-            void *q;
-            FPL_TRY(tmp.alloc((size_t)no * sizeof(float) + 64, &q));
-            cdst = (float *)q;
-          }
-          {
-            TimedLaunch tl(ctx, "mfma_concat_f32");
-            concat_view_f32<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(
-                a.p, a.D, a.C, a.up, a.crop, b.p, b.D, b.C, b.up, b.crop, cdst, no, a.dim);
-          }
-          FPL_HIP(ctx, hipGetLastError());
-          o = View();
-          o.p = cdst; o.D = o.H = o.W = o.dim = a.dim; o.C = a.C + b.C;
-          view[op.dst] = o;
-          continue;
-        }
-        o = a; o.p = nullptr; o.dim = a.dim; o.C = a.C + b.C;
-        view[op.dst] = o;
-        continue;
-      }
-      default: break;
-    }
-    // conv3 -> conv1 (-> pool2) run as ONE kernel when the intermediate tensors have no
-    // other reader: the 1x1x1 conv is chained in registers, the pool is an epilogue
-    // (FPL_F32_UNFUSED=1: one kernel per op, for A/B runs)
-    int fuse1 = -1, fusep = -1;
-    if (op.kind == FPL_OP_CONV && op.k == 3 && i + 1 < prog->ops.size() && !getenv("FPL_F32_UNFUSED")) {
-      auto readers = [&](int t) {
-        int cnt = t == prog->out_tensor ? 1 : 0;
-        for (auto &o2 : prog->ops) cnt += (o2.src0 == t) + (o2.src1 == t);
-        return cnt;
-      };
-      const fpl_op &n1 = prog->ops[i + 1];
-      const int mb0 = (op.cout + 15) / 16, mb1 = (n1.cout + 15) / 16;
-      const bool pair_ok = (mb0 == mb1) && (mb0 == 2 || mb0 == 3 || mb0 == 4) && op.cout % 4 == 0;
-      if (n1.kind == FPL_OP_CONV && n1.k == 1 && n1.src0 == op.dst && readers(op.dst) == 1 &&
-          pair_ok && (op.act == FPL_ACT_RELU || op.act == FPL_ACT_NONE)) {
-        fuse1 = (int)i + 1;
-        if (i + 2 < prog->ops.size()) {
-          const fpl_op &n2 = prog->ops[i + 2];
-          if (n2.kind == FPL_OP_POOL && n2.src0 == n1.dst && readers(n1.dst) == 1 &&
-              n2.p[0] == 2 && n2.p[1] == 2 && n2.p[2] == 2 &&
-              (n1.act == FPL_ACT_RELU || n1.act == FPL_ACT_NONE))
-            fusep = (int)i + 2;
-        }
-        // the Cin = 1 kernel exists only in its pooled form (mb 2 / 3); a virtual input
-        // (up / crop / concat views are fine for the multi-channel kernel)
-        if (op.cin == 1 && (fusep < 0 || mb0 == 4)) fuse1 = fusep = -1;
-      }
-    }
-    float *dst;
-    int od = 0, oc = 0;
-    if (op.kind == FPL_OP_CONV) { od = a.dim - (op.k - 1); oc = op.cout; }
-    if (op.kind == FPL_OP_POOL) { od = a.dim / 2; oc = a.C; }
-    if (op.kind == FPL_OP_ADD) { od = a.dim; oc = a.C; }
-    if (op.kind == FPL_OP_DECONV) { od = 2 * a.dim; oc = op.cout; }
-    if (op.kind == FPL_OP_DOWN) { od = a.dim / 2; oc = op.cout; }      // sizes as a pool's
-    if (op.kind == FPL_OP_DILATED) { od = a.dim - 4; oc = op.cout; }
-    FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
-    const int od_conv = od;                       // conv3's own output edge
-    const fpl_op &last = fusep >= 0 ? prog->ops[fusep] : (fuse1 >= 0 ? prog->ops[fuse1] : op);
-    if (fuse1 >= 0) { oc = prog->ops[fuse1].cout; if (fusep >= 0) od = od / 2; }
-    FPL_REQUIRE(ctx, od > 0, "op %zu: tile %d is too small for this architecture", i, T);
+    const TensorView a = seen(s.src[0]), b = s.n_src > 1 ? seen(s.src[1]) : TensorView();
+    if (s.form == ADD)
+      FPL_REQUIRE(ctx, a.dim == b.dim, "op %d: add of incompatible tensors", i);
+    else if (s.n_src > 1)
+      FPL_REQUIRE(ctx, a.dim == b.dim, "op %d: concatenate of %d^3 with %d^3 - input size is "
+                  "not compatible with this architecture", i, a.dim, b.dim);
     // extents of the result: cubic, but for the voxel GEMMs, which follow their input's
-    int oD = od, oH = od, oW = od;
-    if (op.kind == FPL_OP_DECONV) { oD = 2 * a.D; oH = 2 * a.H; oW = 2 * a.W; }
-    else if (op.kind == FPL_OP_DOWN) { oD = a.D / 2; oH = a.H / 2; oW = a.W / 2; }
-    else if (op.kind == FPL_OP_DILATED) { oD = a.D - 4; oH = a.H - 4; oW = a.W - 4; }
-    else if (op.kind == FPL_OP_CONV && op.k == 1) { oD = a.D; oH = a.H; oW = a.W; }
-    FPL_REQUIRE(ctx, oD > 0 && oH > 0 && oW > 0, "op %zu: tile %d is too small for this architecture", i, T);
-    if (last.dst == prog->out_tensor) {
-      dst = out;
-    } else {
+    const int od_conv = a.dim - 2;                // a 3x3x3's own output edge
+    int oD, oH, oW, oc = prog->ops[s.op[s.mb1 ? 1 : 0]].cout;
+    switch (s.form) {
+      case CONV1: oD = a.D; oH = a.H; oW = a.W; break;
+      case DECONV: oD = 2 * a.D; oH = 2 * a.H; oW = 2 * a.W; break;
+      case DOWN: oD = a.D / 2; oH = a.H / 2; oW = a.W / 2; break;      // sizes as a pool's
+      case ATROUS: oD = a.D - 4; oH = a.H - 4; oW = a.W - 4; break;
+      case POOL: oD = oH = oW = a.dim / 2; oc = a.C; break;
+      case ADD: oD = oH = oW = a.dim; oc = a.C; break;
+      case CONCAT: oD = oH = oW = a.dim; oc = a.C + b.C; break;
+      default: oD = oH = oW = s.pool ? od_conv / 2 : od_conv; break;
+    }
+    FPL_REQUIRE(ctx, oD > 0 && oH > 0 && oW > 0, "op %d: tile %d is too small for this architecture", i, T);
+    float *dst = out;
+    if (s.dst != prog->out_tensor) {
       void *q;
       FPL_TRY(tmp.alloc((size_t)n * oD * oH * oW * oc * sizeof(float) + 64, &q));
       dst = (float *)q;
     }
-    o.p = dst; o.D = oD; o.H = oH; o.W = oW; o.C = oc; o.dim = od;
-    if (op.kind == FPL_OP_DECONV) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: Conv3DTranspose of a view", i);
-      DeconvF c;
-      c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
-      c.nb2 = (2 * op.cout + 15) / 16;
-      c.w = st->frags + st->off[i];
-      c.shift = c.w + (size_t)4 * c.nb2 * ((op.cin + 15) / 16) * 256;
-      c.act = op.act; c.out = dst; c.cout = op.cout;
-      FPL_TRY(launch_deconv(ctx, c));
-    } else if (op.kind == FPL_OP_DOWN) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: strided Conv3D of a view", i);
-      FPL_REQUIRE(ctx, oD > 0 && oH > 0 && oW > 0, "op %zu: tile %d is too small for this architecture", i, T);
-      int nkb_reg, nbt;
-      down_form(op.cin, &nkb_reg, &nbt);
-      DownF c;
-      c.in = a.p; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
-      c.OD = oD; c.OH = oH; c.OW = oW; c.M = (int64_t)n * oD * oH * oW;
-      c.nbp = ((op.cout + 15) / 16 + nbt - 1) / nbt * nbt;
-      c.w = st->frags + st->off[i];
-      c.shift = c.w + (size_t)4 * ((2 * op.cin + 15) / 16) * c.nbp * 256;
-      c.act = op.act; c.out = dst; c.cout = op.cout;
-      FPL_TRY(launch_down(ctx, c));
-    } else if (op.kind == FPL_OP_DILATED) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == op.cin, "op %zu: dilated Conv3D of a view", i);
-      AtrousF c;
-      c.in = a.p; c.D = a.D; c.H = a.H; c.W = a.W; c.C = a.C; c.ncc = (a.C + 15) / 16;
-      c.act = op.act; c.opitch = op.cout;                  // (the output extents are the input's - 4)
-      size_t woff = st->off[i];
-      for (int c0 = 0; c0 < op.cout; c0 += 64) {      // 64 output channels per launch
-        const int cs = std::min(64, op.cout - c0), mb = (cs + 15) / 16;
-        c.w = st->frags + woff; c.shift = prog->arena_dev + op.shift_off + c0;
-        c.out = dst + c0; c.cout = cs;
-        woff += (size_t)c.ncc * 27 * mb * 256;
-        switch (mb) {
-          case 1: FPL_TRY(launch_atrous<1>(ctx, c, n)); break;
-          case 2: FPL_TRY(launch_atrous<2>(ctx, c, n)); break;
-          case 3: FPL_TRY(launch_atrous<3>(ctx, c, n)); break;
-          case 4: FPL_TRY(launch_atrous<4>(ctx, c, n)); break;
+    const int64_t no = (int64_t)n * oD * oH * oW * oc;
+    const float *w = st->frags + s.frag_off;
+    switch (s.form) {
+      case CONCAT: {
+        TimedLaunch tl(ctx, "mfma_concat_f32");
+        concat_view_f32<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(
+            a.p, a.D, a.C, a.up, a.crop, b.p, b.D, b.C, b.up, b.crop, dst, no, a.dim);
+        break;
+      }
+      case ADD: {
+        TimedLaunch tl(ctx, "mfma_add_f32");
+        add_view_f32<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(a.p, a.D, a.crop, b.p, b.D, b.crop,
+                                                                     dst, no, oD, oc, op.act);
+        break;
+      }
+      case POOL: {
+        TimedLaunch tl(ctx, "mfma_pool_f32");
+        pool2_f32v<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(a.p, dst, no, a.D, a.D, a.D, a.C, oD, oD, oD);
+        break;
+      }
+      case DECONV: {
+        DeconvF c;
+        c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
+        c.nb2 = deconv_nb2(op.cout);
+        c.w = w; c.shift = w + s.shift_off;
+        c.act = op.act; c.out = dst; c.cout = op.cout;
+        FPL_TRY(launch_deconv(ctx, c));
+        break;
+      }
+      case DOWN: {
+        DownF c;
+        c.in = a.p; c.cin = op.cin; c.D = a.D; c.H = a.H; c.W = a.W;
+        c.OD = oD; c.OH = oH; c.OW = oW; c.M = (int64_t)n * oD * oH * oW;
+        c.nbp = down_nbp(op.cin, op.cout);
+        c.w = w; c.shift = w + s.shift_off;
+        c.act = op.act; c.out = dst; c.cout = op.cout;
+        FPL_TRY(launch_down(ctx, c));
+        break;
+      }
+      case ATROUS: {
+        AtrousF c;
+        c.in = a.p; c.D = a.D; c.H = a.H; c.W = a.W; c.C = a.C; c.ncc = (a.C + 15) / 16;
+        c.act = op.act; c.opitch = op.cout;                  // (the output extents are the input's - 4)
+        for (int q = 0; q < s.n_slices; ++q) {               // 64 output channels per launch
+          const Slice &sl = s.slice[q];
+          c.w = st->frags + sl.frag_off; c.shift = prog->arena_dev + op.shift_off + sl.c0;
+          c.out = dst + sl.c0; c.cout = sl.cs;
+          switch (sl.mb) {
+            case 1: FPL_TRY(launch_atrous<1>(ctx, c, n)); break;
+            case 2: FPL_TRY(launch_atrous<2>(ctx, c, n)); break;
+            case 3: FPL_TRY(launch_atrous<3>(ctx, c, n)); break;
+            case 4: FPL_TRY(launch_atrous<4>(ctx, c, n)); break;
+            default: return no_instance(ctx, s, sl.mb);
+          }
         }
+        break;
       }
-    } else if (op.kind == FPL_OP_ADD) {
-      const View b = view[op.src1];
-      FPL_REQUIRE(ctx, a.p && b.p && a.up == 1 && b.up == 1 && a.dim == b.dim && a.C == b.C,
-                  "op %zu: add of incompatible tensors", i);
-      const int64_t no = (int64_t)n * cube(od) * oc;
-      TimedLaunch tl(ctx, "mfma_add_f32");
-      add_view_f32<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(a.p, a.D, a.crop, b.p, b.D, b.crop,
-                                                                   dst, no, od, oc, op.act);
-    } else if (op.kind == FPL_OP_POOL) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0, "op %zu: pool of a view", i);
-      const int64_t no = (int64_t)n * cube(od) * oc;
-      TimedLaunch tl(ctx, "mfma_pool_f32");
-      pool2_f32v<<<(unsigned)ceil_div64(no, 256), 256, 0, stm>>>(a.p, dst, no, a.D, a.D, a.D, a.C, od, od, od);
-    } else if (op.k == 1) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0, "op %zu: conv1 of a view", i);
-      Conv1F c;
-      c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin;
-      c.w = st->frags + st->off[i]; c.shift = prog->arena_dev + op.shift_off; c.act = op.act;
-      c.out = dst; c.cout = op.cout; c.stats = nullptr;
-      const int mb = (op.cout + 15) / 16;
-      switch (mb) {
-        case 1: FPL_TRY(launch1<1>(ctx, c)); break;
-        case 2: FPL_TRY(launch1<2>(ctx, c)); break;
-        case 3: FPL_TRY(launch1<3>(ctx, c)); break;
-        case 4: FPL_TRY(launch1<4>(ctx, c)); break;
-        case 6: FPL_TRY(launch1<6>(ctx, c)); break;
-        case 8: FPL_TRY(launch1<8>(ctx, c)); break;
-        default: return fpl_fail(ctx, "op %zu: conv1 with %d output channels", i, op.cout);
-      }
-    } else if (op.cin == 1) {
-      FPL_REQUIRE(ctx, a.p && a.up == 1 && a.crop == 0 && a.C == 1, "op %zu: stem of a view", i);
-      StemF c;
-      c.in = a.p; c.D = c.H = c.W = a.D;
-      c.w = st->frags + st->off[i]; c.shift = prog->arena_dev + op.shift_off; c.act = op.act;
-      c.out = dst; c.cout = op.cout; c.OD = c.OH = c.OW = od_conv; c.stats = nullptr;
-      const int mb = (op.cout + 15) / 16;
-      if (fusep >= 0) {
-        const fpl_op &n1 = prog->ops[fuse1];
-        c.w1 = st->frags + st->off[fuse1]; c.shift1 = prog->arena_dev + n1.shift_off;
-        c.act1 = n1.act; c.cout1 = n1.cout;
-        if (mb == 2) FPL_TRY((launch_stem_fused<2, 2>(ctx, c, n)));
-        else FPL_TRY((launch_stem_fused<3, 3>(ctx, c, n)));
-      } else
-      switch (mb) {
-        case 1: FPL_TRY(launch_stem<1>(ctx, c, n)); break;
-        case 2: FPL_TRY(launch_stem<2>(ctx, c, n)); break;
-        case 3: FPL_TRY(launch_stem<3>(ctx, c, n)); break;
-        case 4: FPL_TRY(launch_stem<4>(ctx, c, n)); break;
-        default: return fpl_fail(ctx, "op %zu: stem with %d output channels", i, op.cout);
-      }
-    } else {
-      Conv3F c;
-      c.ncc = 0;
-      auto add_src = [&](const View &v) {
-        const int chunks = (v.C + 15) / 16;
-        for (int q = 0; q < chunks; ++q) {
-          SrcF s;
-          s.p = v.p; s.D = s.H = s.W = v.D; s.C = v.C; s.ch0 = 16 * q;
-          s.up = v.up; s.crop = v.crop; s.pad = 0;
-          c.src[c.ncc++] = s;
+      case CONV1: {
+        Conv1F c;
+        c.in = a.p; c.M = (int64_t)n * a.D * a.H * a.W; c.cin = op.cin;
+        c.w = w; c.shift = prog->arena_dev + op.shift_off; c.act = op.act;
+        c.out = dst; c.cout = op.cout; c.stats = nullptr;
+        switch (s.mb) {                                      // CONV1_MB
+          case 1: FPL_TRY(launch1<1>(ctx, c)); break;
+          case 2: FPL_TRY(launch1<2>(ctx, c)); break;
+          case 3: FPL_TRY(launch1<3>(ctx, c)); break;
+          case 4: FPL_TRY(launch1<4>(ctx, c)); break;
+          case 6: FPL_TRY(launch1<6>(ctx, c)); break;
+          case 8: FPL_TRY(launch1<8>(ctx, c)); break;
+          default: return no_instance(ctx, s, s.mb);
         }
-      };
-      // a concat input is resolved through the producing op
-      bool done = false;
-      for (size_t j = 0; j < i && !done; ++j)
-        if (prog->ops[j].dst == op.src0 && prog->ops[j].kind == FPL_OP_CONCAT) {
-          const View va = view[prog->ops[j].src0], vb = view[prog->ops[j].src1];
-          FPL_REQUIRE(ctx, va.p && vb.p && va.C % 16 == 0, "op %zu: unsupported concat", i);
-          add_src(va);
-          add_src(vb);
-          done = true;
+        break;
+      }
+      case STEM: case STEM_CONV1_POOL: {
+        StemF c;
+        c.in = a.p; c.D = c.H = c.W = a.D;
+        c.w = w; c.shift = prog->arena_dev + op.shift_off; c.act = op.act;
+        c.out = dst; c.cout = op.cout; c.OD = c.OH = c.OW = od_conv; c.stats = nullptr;
+        if (s.form == STEM_CONV1_POOL) {
+          const fpl_op &n1 = prog->ops[s.op[1]];
+          c.w1 = st->frags + s.frag1_off; c.shift1 = prog->arena_dev + n1.shift_off;
+          c.act1 = n1.act; c.cout1 = n1.cout;
+          switch (s.mb) {                                    // STEM_FUSED_MB
+            case 2: FPL_TRY((launch_stem_fused<2, 2>(ctx, c, n))); break;
+            case 3: FPL_TRY((launch_stem_fused<3, 3>(ctx, c, n))); break;
+            default: return no_instance(ctx, s, s.mb);
+          }
+          break;
         }
-      if (!done) {
-        FPL_REQUIRE(ctx, a.p, "op %zu: conv3 of an unmaterialised tensor", i);
-        add_src(a);
-      }
-      // the packed fragments assume channel chunks of the concatenated tensor in
-      // order, each source starting on a 16-channel boundary
-      c.act = op.act; c.opitch = op.cout; c.OD = c.OH = c.OW = od_conv;
-      c.w1 = nullptr; c.shift1 = nullptr; c.act1 = 0; c.cout1 = 0;
-      if (fuse1 >= 0) {
-        const fpl_op &n1 = prog->ops[fuse1];
-        const int mb = (op.cout + 15) / 16;
-        c.w = st->frags + st->off[i]; c.shift = prog->arena_dev + op.shift_off;
-        c.out = dst; c.cout = op.cout; c.opitch = n1.cout;
-        c.w1 = st->frags + st->off[fuse1]; c.shift1 = prog->arena_dev + n1.shift_off;
-        c.act1 = n1.act; c.cout1 = n1.cout;
-        const bool pl = fusep >= 0;
-        if (mb == 2) FPL_TRY(pl ? (launch3_fused<2, 2, true>(ctx, c, n)) : (launch3_fused<2, 2, false>(ctx, c, n)));
-        else if (mb == 3) FPL_TRY(pl ? (launch3_fused<3, 3, true>(ctx, c, n)) : (launch3_fused<3, 3, false>(ctx, c, n)));
-        else FPL_TRY(pl ? (launch3_fused<4, 4, true>(ctx, c, n)) : (launch3_fused<4, 4, false>(ctx, c, n)));
-      } else {
-      size_t woff = st->off[i];
-      for (int c0 = 0; c0 < op.cout; c0 += 64) {      // 64 output channels per launch
-        const int cs = std::min(64, op.cout - c0), mb = (cs + 15) / 16;
-        c.w = st->frags + woff; c.shift = prog->arena_dev + op.shift_off + c0;
-        c.out = dst + c0; c.cout = cs;
-        woff += (size_t)c.ncc * 27 * mb * 256;
-        switch (mb) {
-          case 1: FPL_TRY(launch3<1>(ctx, c, n)); break;
-          case 2: FPL_TRY(launch3<2>(ctx, c, n)); break;
-          case 3: FPL_TRY(launch3<3>(ctx, c, n)); break;
-          case 4: FPL_TRY(launch3<4>(ctx, c, n)); break;
+        switch (s.mb) {
+          case 1: FPL_TRY(launch_stem<1>(ctx, c, n)); break;
+          case 2: FPL_TRY(launch_stem<2>(ctx, c, n)); break;
+          case 3: FPL_TRY(launch_stem<3>(ctx, c, n)); break;
+          case 4: FPL_TRY(launch_stem<4>(ctx, c, n)); break;
+          default: return no_instance(ctx, s, s.mb);
         }
+        break;
       }
+      case CONV3: case CONV3_CONV1: case CONV3_CONV1_POOL: {
+        // channel chunks of the (concatenated) input in order, as the fragments were packed: each
+        // source starts on a 16-channel boundary
+        Conv3F c;
+        c.ncc = 0;
+        for (int q = 0; q < s.n_src; ++q) {
+          const TensorView &v = q ? b : a;
+          const int chunks = (v.C + 15) / 16;
+          FPL_REQUIRE(ctx, c.ncc + chunks <= CONV3_CHUNKS_MAX, "op %d: more than %d channel chunks", i, CONV3_CHUNKS_MAX);
+          for (int k = 0; k < chunks; ++k) {
+            SrcF src;
+            src.p = v.p; src.D = src.H = src.W = v.D; src.C = v.C; src.ch0 = 16 * k;
+            src.up = v.up; src.crop = v.crop; src.pad = 0;
+            c.src[c.ncc++] = src;
+          }
+        }
+        c.act = op.act; c.opitch = op.cout; c.OD = c.OH = c.OW = od_conv;
+        c.w1 = nullptr; c.shift1 = nullptr; c.act1 = 0; c.cout1 = 0;
+        if (s.mb1) {
+          const fpl_op &n1 = prog->ops[s.op[1]];
+          c.opitch = n1.cout;
+          c.w1 = st->frags + s.frag1_off; c.shift1 = prog->arena_dev + n1.shift_off;
+          c.act1 = n1.act; c.cout1 = n1.cout;
+        }
+        for (int q = 0; q < s.n_slices; ++q) {               // 64 output channels per launch
+          const Slice &sl = s.slice[q];
+          c.w = st->frags + sl.frag_off; c.shift = prog->arena_dev + op.shift_off + sl.c0;
+          c.out = dst + sl.c0; c.cout = sl.cs;
+          const int inst = 100 * s.form + sl.mb;
+          // FUSED_MB for the chained forms.  (The cases stand in the order in which the kernels
+          // have always been instantiated: the code object keeps its layout)
+          switch (inst) {
+            case 100 * CONV3_CONV1_POOL + 2: FPL_TRY((launch3_fused<2, 2, true>(ctx, c, n))); break;
+            case 100 * CONV3_CONV1 + 2: FPL_TRY((launch3_fused<2, 2, false>(ctx, c, n))); break;
+            case 100 * CONV3_CONV1_POOL + 3: FPL_TRY((launch3_fused<3, 3, true>(ctx, c, n))); break;
+            case 100 * CONV3_CONV1 + 3: FPL_TRY((launch3_fused<3, 3, false>(ctx, c, n))); break;
+            case 100 * CONV3_CONV1_POOL + 4: FPL_TRY((launch3_fused<4, 4, true>(ctx, c, n))); break;
+            case 100 * CONV3_CONV1 + 4: FPL_TRY((launch3_fused<4, 4, false>(ctx, c, n))); break;
+            case 100 * CONV3 + 1: FPL_TRY(launch3<1>(ctx, c, n)); break;
+            case 100 * CONV3 + 2: FPL_TRY(launch3<2>(ctx, c, n)); break;
+            case 100 * CONV3 + 3: FPL_TRY(launch3<3>(ctx, c, n)); break;
+            case 100 * CONV3 + 4: FPL_TRY(launch3<4>(ctx, c, n)); break;
+            default: return no_instance(ctx, s, sl.mb);
+          }
+        }
+        break;
       }
+      default:
+        return fpl_fail(ctx, "op %d: the plan holds an unknown step form %d", i, s.form);
     }
     FPL_HIP(ctx, hipGetLastError());
-    if (fuse1 >= 0) {                 // the fused ops are done: their result is `last`'s
-      view[last.dst] = o;
-      i = (size_t)(fusep >= 0 ? fusep : fuse1);
-      continue;
-    }
-    view[op.dst] = o;
+    TensorView o;
+    o.p = dst; o.D = oD; o.H = oH; o.W = oW; o.C = oc; o.dim = oD;
+    buf[s.dst] = o;
   }
   return 0;
 }

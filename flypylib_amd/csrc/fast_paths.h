@@ -84,14 +84,16 @@ FPL_DECLARE_H16_PATHS(f16)
 // split IEEE halves (conv_mfma.hip built with -DFPL_SPLIT): only the fpl_unet_* pair exists
 FPL_DECLARE_H16_PATHS(f16s)
 
-// fp32 MFMA executor over any lowered program without ADD (conv_mfma_f32.hip):
-// cubic tiles (n, T,T,T) f32 -> network output (n, d,d,d, c) f32
+// fp32 MFMA executor over the lowered programs its plan accepts (conv_mfma_f32.hip,
+// mfma_f32_plan.h): cubic tiles (n, T,T,T) f32 -> network output (n, d,d,d, c) f32
 bool fpl_mfma_f32_supported(const fpl_program *prog);
 int fpl_forward_mfma_f32(fpl_ctx *ctx, fpl_program *prog, const float *in, int n, int T,
                          float *out);
 // the same on (n, dims) tiles of any extents, for programs of voxel GEMMs (1x1x1 convs,
-// Conv3DTransposes, strided Conv3D(2)s) and dilated Conv3Ds only: fpl_mfma_f32_any_dims
-bool fpl_mfma_f32_any_dims(const fpl_program *prog);
+// Conv3DTransposes, strided Conv3D(2)s) and dilated Conv3Ds only (Plan::any_dims).
+// fpl_mfma_f32_takes: the dispatcher's one question - supported, and on tiles that are not cubic
+// such a program that is not made of 1x1x1 convs alone
+bool fpl_mfma_f32_takes(const fpl_program *prog, bool cubic);
 int fpl_forward_mfma_f32_dims(fpl_ctx *ctx, fpl_program *prog, const float *in, int n,
                               const int32_t dims[3], float *out);
 

@@ -191,8 +191,7 @@ int fpl_program_forward(fpl_ctx *ctx, fpl_program *prog, const float *in,
   const bool cubic = in_dims[0] == in_dims[1] && in_dims[1] == in_dims[2];
   // (a program that holds a Conv3DTranspose, a strided Conv3D(2) or a dilated Conv3D and nothing else
   // but voxel GEMMs runs on any extents)
-  const bool any_dims = (has_deconv(prog) || has_down(prog) || has_dilated(prog)) && fpl_mfma_f32_any_dims(prog);
-  if ((cubic || any_dims) && fpl_mfma_f32_supported(prog) && !getenv("FPL_FORCE_PEROP")) {
+  if (fpl_mfma_f32_takes(prog, cubic) && !getenv("FPL_FORCE_PEROP")) {
     set_last_path(ctx, "mfma_f32");
     FPL_TRY(fpl_forward_mfma_f32_dims(ctx, prog, in_dev, n, in_dims, net_out));
   } else {

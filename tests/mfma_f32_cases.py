@@ -1,6 +1,7 @@
 """Cases, float64 references and bounds of the op-by-op tests of the fp32 MFMA executor
-(csrc/conv_mfma_f32.hip: fpl_mfma_f32_supported, fpl_forward_mfma_f32_dims and the inference
-kernels they launch): test_mfma_f32_cases_host.py (what each case exercises and that its bound is
+(csrc/mfma_f32_plan.h: the plan that says what it runs and how; csrc/conv_mfma_f32.hip:
+fpl_forward_mfma_f32_dims, which launches from it, and the inference kernels):
+test_mfma_f32_cases_host.py (what each case exercises and that its bound is
 sound, on the CPU) and test_gpu_mfma_f32.py.  Nothing here touches a GPU.
 
 THE BOUND of one convolution (`conv_case`), from the kernels' own rounding sequence:
@@ -29,15 +30,18 @@ TWO LAYERS (`fused_case`): with a = act(conv3(h)) and B1 the bound above for it,
 gamma(K2) * ((|a| + B1) (*) |W1| + |b1|), K2 = c3 + 2, since |a_gpu| <= |a| + B1.  The bound is
 their sum; a max pool takes the largest bound of its window (|max a - max b| <= max |a - b|).
 
-`predict_launches` restates the dispatcher in plain Python: which TimedLaunch names, and how many of
-each, a program must produce.  A case that lands on another kernel than intended fails on that."""
+`supported_ops`, `fusion` and `predict_launches_ops` restate, in plain Python, the rules that stood
+inline in conv_mfma_f32.hip before the plan header existed: which programs the executor takes, and
+which TimedLaunch names, and how many of each, a program must produce.  They are the record the
+header is held to (test_mfma_f32_plan_host.py), not a reading of it.  A case that lands on another
+kernel than intended fails on that."""
 import collections
 import functools
 
 import numpy as np
 
 from flypylib_amd.program import (ACT_NONE, ACT_RELU, BN_EPS, LayerGraph, OP_ADD, OP_CONCAT, OP_CONV, OP_CROP,
-                                  OP_POOL, OP_UP)
+                                  OP_DECONV, OP_DILATED, OP_DOWN, OP_POOL, OP_UP)
 from tests.perop_cases import TINY, U, _W5, _W7, _conv64, _ints, gamma, np_crop, np_lift, np_pool, np_up
 
 BATCH = 3                          # every GPU run is made on x and on x[:1]
@@ -49,22 +53,43 @@ def _mb(c):
     return (c + 15) // 16
 
 
-def supported(graph):
-    """fpl_mfma_f32_supported for the op kinds of these cases (conv, pool, up, crop, concat, add)"""
-    ops = graph.lower_inference()[0]
-    out_tensor = graph.lower_inference()[2]
-    view, ch, cat_first = {0: 0}, {0: 1}, {0: 0}
+def _conv3m(o):
+    return o['kind'] == OP_CONV and o['k'] == 3 and o['cin'] > 1
+
+
+def concats_written(ops, out_tensor):
+    """per op: a concatenation that is written out.  In a program that holds a Conv3DTranspose, one
+    whose readers are not all multi-channel 3x3x3 convs (the program's output counts as a reader)"""
+    other = {out_tensor}
     for o in ops:
+        if not _conv3m(o):
+            other.update(t for t in (o['src0'], o['src1']) if t >= 0)
+    deconv = any(o['kind'] == OP_DECONV for o in ops)
+    return [deconv and o['kind'] == OP_CONCAT and o['dst'] in other for o in ops]
+
+
+def supported_ops(ops, out_tensor):
+    """the acceptance rule of the fp32 MFMA executor as it stood inline in conv_mfma_f32.hip before
+    csrc/mfma_f32_plan.h existed (fpl_mfma_f32_supported with its concats_written), restated"""
+    written = concats_written(ops, out_tensor)
+    view, ch, cat_first = {0: 0}, {0: 1}, {0: 0}
+    for i, o in enumerate(ops):
         kind, s0, s1, d = o['kind'], o['src0'], o['src1'], o['dst']
         v0, v1 = view[s0], view[s1] if s1 >= 0 else 0
-        view[d], ch[d], cat_first[d] = 0, o['cout'], 0
+        view[d], cat_first[d] = 0, 0
+        ch[d] = o['cout'] if kind in (OP_CONV, OP_DECONV, OP_DOWN, OP_DILATED) else ch[s0]
         if kind == OP_CONCAT:
-            cat_first[d], view[d] = ch[s0], 2
+            ch[d], cat_first[d] = ch[s0] + ch[s1], ch[s0]
+            if written[i]:
+                if v0 == 2 or v1 == 2:
+                    return False
+            else:
+                view[d] = 2
         elif kind in (OP_UP, OP_CROP):
             if v0:
                 return False
             view[d] = 1
-        elif kind == OP_CONV and o['k'] == 3 and o['cin'] > 1:
+        elif _conv3m(o):
             if v1 or cat_first[s0] % 16:
                 return False
         elif kind == OP_ADD:
@@ -83,12 +108,60 @@ def supported(graph):
             return False
         if kind == OP_CONV and o['k'] == 1 and _mb(o['cout']) not in (1, 2, 3, 4, 6, 8):
             return False
+        if kind in (OP_DECONV, OP_DOWN) and (o['k'] != 2 or o['cin'] > 256 or o['cout'] > 256):
+            return False
+        if kind == OP_DILATED and (o['k'] != 3 or o['cout'] > 256 or o['cin'] > 192):
+            return False
     return True
 
 
+def supported(graph):
+    """`supported_ops` of a graph's lowered program"""
+    ops, _, out_tensor, _ = graph.lower_inference()
+    return supported_ops(ops, out_tensor)
+
+
+def launch_refusal(ops, out_tensor):
+    """For a program `supported_ops` accepts: the error with which the launch loop of that time then
+    refused it (its structural FPL_REQUIREs, restated with its view bookkeeping), or None where it
+    ran.  The dispatchers had picked the executor by then, so such a call failed; the plan declines
+    these programs and they run on the per-op executor."""
+    written = concats_written(ops, out_tensor)
+    buf = dict(p=True, up=1, crop=0)
+    view, made_by = {0: buf}, {}
+    for i, o in enumerate(ops):
+        kind, d = o['kind'], o['dst']
+        a, b = view[o['src0']], view.get(o['src1'])
+        made_by[d] = o
+        if kind in (OP_UP, OP_CROP):
+            if a['up'] != 1 or a['crop'] != 0:
+                return 'nested views'
+            view[d] = dict(a, up=o['p'][0]) if kind == OP_UP else dict(a, crop=o['p'][0])
+            continue
+        if kind == OP_CONCAT:
+            if written[i] and not (a['p'] and b['p']):
+                return 'concatenate of a concatenation'
+            view[d] = buf if written[i] else dict(a, p=False)
+            continue
+        if kind == OP_ADD:
+            if not (a['p'] and b['p'] and a['up'] == 1 and b['up'] == 1):
+                return 'add of incompatible tensors'
+        elif _conv3m(o):
+            cat = made_by.get(o['src0'])
+            if cat is not None and cat['kind'] == OP_CONCAT:
+                if not (view[cat['src0']]['p'] and view[cat['src1']]['p']):
+                    return 'unsupported concat'
+            elif not a['p']:
+                return 'conv3 of an unmaterialised tensor'
+        elif not (a['p'] and a['up'] == 1 and a['crop'] == 0):
+            return 'of a view'
+        view[d] = buf
+    return None
+
+
 def fusion(ops, i, out_tensor):
-    """the rule of fpl_forward_mfma_f32_dims for the 3x3x3 conv ops[i]: (fuses the 1x1x1 conv that
-    follows, fuses the pool after that)"""
+    """the fusion rule for the 3x3x3 conv ops[i], as fpl_forward_mfma_f32_dims stated it inline: (fuses
+    the 1x1x1 conv that follows, fuses the pool after that)"""
     op = ops[i]
     if op['kind'] != OP_CONV or op['k'] != 3 or i + 1 >= len(ops):
         return False, False
@@ -112,11 +185,17 @@ def fusion(ops, i, out_tensor):
 
 
 def predict_launches(graph, unfused=False):
-    """{TimedLaunch name: launches} of one forward on the fp32 MFMA executor, or None where
-    `supported` declines the program (the dispatcher then takes the per-op executor)"""
-    if not supported(graph):
-        return None
+    """`predict_launches_ops` of a graph's lowered program"""
     ops, _, out_tensor, _ = graph.lower_inference()
+    return predict_launches_ops(ops, out_tensor, unfused)
+
+
+def predict_launches_ops(ops, out_tensor, unfused=False):
+    """{TimedLaunch name: launches} of one forward on the fp32 MFMA executor, or None where
+    `supported_ops` declines the program (the dispatcher then takes the per-op executor)"""
+    if not supported_ops(ops, out_tensor):
+        return None
+    written = concats_written(ops, out_tensor)
     n = collections.Counter()
     i = 0
     while i < len(ops):
@@ -125,6 +204,14 @@ def predict_launches(graph, unfused=False):
             n['mfma_pool_f32'] += 1
         elif o['kind'] == OP_ADD:
             n['mfma_add_f32'] += 1
+        elif o['kind'] == OP_DECONV:
+            n['mfma_deconv2_f32'] += 1
+        elif o['kind'] == OP_DOWN:
+            n['mfma_down2_f32'] += 1
+        elif o['kind'] == OP_DILATED:
+            n['mfma_atrous3_f32'] += -(-o['cout'] // 64)             # slices of 64 outputs
+        elif o['kind'] == OP_CONCAT and written[i]:
+            n['mfma_concat_f32'] += 1
         elif o['kind'] == OP_CONV and o['k'] == 1:
             n['mfma_conv1_f32'] += 1
         elif o['kind'] == OP_CONV:

@@ -317,3 +317,32 @@ def test_evaluate_in_inference_mode(ctx):
     margin = float(np.mean(TOL / room))
     print('loss', got['loss'], want[0] / want[7], 'margin', margin)
     assert margin < 0.05 * got['loss'] and abs(got['loss'] - want[0] / want[7]) <= margin
+
+
+def _launches_at_tile_6(ctx, monkeypatch, graph, want):
+    """forward of a batch of 3 at input tile 6 on the fp32 MFMA executor: the TimedLaunch names and
+    counts are `want`, the result is the float64 restatement's within TOL"""
+    from tests import mfma_f32_cases as mc
+    from tests.test_gpu_mfma_f32 import _run
+    assert mc.predict_launches(graph) == want
+    x = np.random.default_rng(6).standard_normal((3, 6, 6, 6, 1)).astype(np.float32)
+    got, = _run(ctx, monkeypatch, graph, (x,), want)
+    ref = dc.graph_forward64(graph, x)
+    assert got.shape == ref.shape and float(np.max(np.abs(got - ref))) < TOL
+
+
+def test_launches_of_a_conv3dtranspose_behind_a_lift(ctx, monkeypatch):
+    g, _ = dc.deconv_graph(16, 16, True, True, False, (6, 6, 6))
+    _launches_at_tile_6(ctx, monkeypatch, g, {'mfma_conv1_f32': 1, 'mfma_deconv2_f32': 1})
+
+
+def test_launches_of_a_concatenation_that_a_1x1x1_conv_reads(ctx, monkeypatch):
+    """in a program that holds a Conv3DTranspose such a concatenation is written out"""
+    from flypylib_amd.program import LayerGraph
+    g = LayerGraph((6, 6, 6), seed=5)
+    lift = g.conv(g.input(), 16, 1, use_bias=True)
+    u = g.deconv(g.pool(lift), 16, use_bias=True, activation='relu')
+    g.finish(g.conv(g.concat(u, lift), 8, 1, use_bias=True))
+    dc.randomize(g)
+    _launches_at_tile_6(ctx, monkeypatch, g, {'mfma_conv1_f32': 2, 'mfma_pool_f32': 1, 'mfma_deconv2_f32': 1,
+                                              'mfma_concat_f32': 1})

@@ -341,3 +341,17 @@ def test_fit_save_load_infer_and_evaluate(ctx, tmp_path):
     ref = di.graph_forward64(net.train_single, x)
     assert fwd.shape == ref.shape == y.shape and np.max(np.abs(fwd - ref)) < TOL
     _means_close(got, valid.loss_sums_numpy(fwd, y, 'binary_crossentropy'), ['acc', 'loss'])
+
+
+def test_launches_of_a_dilated_conv_of_two_slices_behind_a_lift(ctx, monkeypatch):
+    """a batch of 3 at input tile 6 on the fp32 MFMA executor: 65 outputs are two launches of the
+    atrous kernel (64 + 1)"""
+    from tests import mfma_f32_cases as mc
+    from tests.test_gpu_mfma_f32 import _run
+    g, _ = di.dilated_graph(16, 65, True, True, False, (6, 6, 6))
+    want = {'mfma_conv1_f32': 1, 'mfma_atrous3_f32': 2}
+    assert mc.predict_launches(g) == want
+    x = np.random.default_rng(6).standard_normal((3, 6, 6, 6, 1)).astype(np.float32)
+    got, = _run(ctx, monkeypatch, g, (x,), want)
+    ref = di.graph_forward64(g, x)
+    assert got.shape == ref.shape == (3, 2, 2, 2, 65) and float(np.max(np.abs(got - ref))) < TOL

@@ -340,3 +340,17 @@ def test_evaluate_in_inference_mode(ctx):
     margin = float(np.mean(TOL / room))
     print('loss', got['loss'], want[0] / want[7], 'margin', margin)
     assert margin < 0.05 * got['loss'] and abs(got['loss'] - want[0] / want[7]) <= margin
+
+
+def test_launches_of_a_strided_conv_behind_a_lift(ctx, monkeypatch):
+    """a batch of 3 at input tile 6 on the fp32 MFMA executor: one launch of the lift's kernel, one of
+    the down-convolution's"""
+    from tests import mfma_f32_cases as mc
+    from tests.test_gpu_mfma_f32 import _run
+    g, _ = dn.down_graph(16, 16, True, True, False, (6, 6, 6))
+    want = {'mfma_conv1_f32': 1, 'mfma_down2_f32': 1}
+    assert mc.predict_launches(g) == want
+    x = np.random.default_rng(6).standard_normal((3, 6, 6, 6, 1)).astype(np.float32)
+    got, = _run(ctx, monkeypatch, g, (x,), want)
+    ref = dn.graph_forward64(g, x)
+    assert got.shape == ref.shape == (3, 3, 3, 3, 16) and float(np.max(np.abs(got - ref))) < TOL

@@ -175,3 +175,54 @@ def test_declined_programs_run_on_the_per_op_executor(ctx, monkeypatch, kind, ci
     assert (c['launches'] is None) == ((kind, cin, cout, tile, lifts) in mc.DECLINED_CASES)
     got = _both_batches(ctx, monkeypatch, c['graph'], c['x'], c['launches'])
     _within(got, c, 'path %s' % ctx.last_path())
+
+
+# ---- 6. programs the acceptance rule once took and the launch loop then refused ----------------
+MOVED_CASES = ('add_of_an_up_view', 'add_of_a_virtual_concat', 'conv3_of_a_concat_of_a_concat')
+
+
+def _moved_case(name):
+    """graph, x, ref (float64 oracle on the lifts' float32 values: one correctly rounded product per
+    element, as the GPU's fma(x, w, 0) gives), bound (perop_cases: gamma(K) on the magnitudes, K =
+    k^3 cin + 1 for the conv; one rounding of the sum for the add)"""
+    from flypylib_amd.program import LayerGraph
+    from tests.perop_cases import TINY, U, _conv64, gamma, np_lift, np_pool, np_up
+    seed = 900 + MOVED_CASES.index(name)
+    tile = 8 if name == 'add_of_an_up_view' else 3
+    g = LayerGraph(tile, seed=seed)
+    x = np.random.default_rng(seed).standard_normal((mc.BATCH, tile, tile, tile, 1)).astype(np.float32)
+
+    def lift(node, h, c):
+        n = g.conv(node, c, 1)
+        return n, np_lift(h, g.weights[n.weight_slots[0]].reshape(-1))
+
+    if name == 'add_of_an_up_view':
+        a, ha = lift(g.pool(g.input(), 2), np_pool(x, 2), 16)          # at tile 4
+        b, hb = lift(g.input(), x, 16)
+        g.finish(g.add(g.up(a, 2), b))
+        ha = np_up(ha, 2)
+    elif name == 'add_of_a_virtual_concat':
+        (a0, h0), (a1, h1), (b, hb) = lift(g.input(), x, 16), lift(g.input(), x, 16), lift(g.input(), x, 32)
+        g.finish(g.add(g.concat(a0, a1), b))
+        ha = np.concatenate([h0, h1], axis=-1)
+    else:
+        a, h = lift(g.input(), x, 16)
+        conv = g.conv(g.concat(g.concat(a, a), a), 16, 3)
+        g.finish(conv)
+        h = np.concatenate([h, h, h], axis=-1)
+        w = g.weights[conv.weight_slots[0]]
+        return dict(graph=g, x=x, ref=_conv64(h, w), bound=gamma(27 * 48 + 1) * _conv64(np.abs(h), np.abs(w)) + TINY)
+    ref = ha.astype(np.float64) + hb.astype(np.float64)
+    return dict(graph=g, x=x, ref=ref, bound=U * np.abs(ref) + TINY)
+
+
+@pytest.mark.parametrize('name', MOVED_CASES)
+def test_programs_the_launch_loop_used_to_refuse_run_on_the_per_op_executor(ctx, monkeypatch, name):
+    """an add of an up-sampled view or of a virtual concatenation, a 3x3x3 conv of a concatenation of
+    a concatenation: accepted once and then refused with an error at launch; the plan
+    (csrc/mfma_f32_plan.h) declines them, so the dispatcher takes the per-op executor"""
+    c = _moved_case(name)
+    ops, _, out_tensor, _ = c['graph'].lower_inference()
+    assert mc.supported_ops(ops, out_tensor) and mc.launch_refusal(ops, out_tensor) is not None
+    got = _both_batches(ctx, monkeypatch, c['graph'], c['x'], None)
+    _within(got, c, name)
